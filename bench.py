@@ -42,6 +42,32 @@ DIRECT_HIT_B = 16 + 8 + 8                      # position + normal + specular re
 COMPOSE_PIXEL_B = 44 + 16 + 4                  # compose reads 44 B, writes 16 B; post writes 4 B (fused: output not re-read)
 COMPOSE_PIXEL_LEAN_B = 4 + 16 + 4              # lean frame, inside direct_kernel: diffuse read, output + back buffer written
 
+# --dump-outputs: bytes written in all (back buffer 40 MB + composed image 20 MB; 1080p RGBA8 as float32 is 33.2 MB and stays whole) and the seed of the pixel sample
+DUMP_BYTES = 60 * 10**6
+DUMP_SHARES = {"final_rgba8": 40 * 10**6, "output_rgba32f": 20 * 10**6}
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, images):
+    """Writes {name: (rows, width, channels) array} as out_dir/<name>.npy in float32.  An image larger than its share of DUMP_BYTES is cut
+    to a sample of its pixels (seeded, sorted, the same for every build at the same size): shape (pixels, channels).  Returns what was written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, img in images.items():
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        ch = img.shape[-1]
+        entry = {"shape": list(img.shape), "dtype": "float32"}
+        if img.nbytes > DUMP_SHARES[name]:
+            n = DUMP_SHARES[name] // (4 * ch)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(img.shape[0] * img.shape[1], n, replace=False))
+            img = img.reshape(-1, ch)[idx]
+            entry.update(shape=list(img.shape), sample={"seed": DUMP_SEED, "pixels": int(n), "of_shape": entry["shape"],
+                                                        "how": "np.sort(np.random.default_rng(seed).choice(rows * width, pixels, replace=False)) over the row-major pixels"})
+        np.save(os.path.join(out_dir, name + ".npy"), img)
+        info[name] = entry
+    return info
+
 
 def parse_args():
     ap = argparse.ArgumentParser()
@@ -81,6 +107,8 @@ def parse_args():
     ap.add_argument("--cpu-baseline-height", type=int, default=0, help="rows of the frame the CPU baseline renders (0 = all)")
     ap.add_argument("--timed-loop-only", action="store_true", help="profiling runs (tools/profile_round.sh): only the timed loop of `value` -- no always_rebuild leg, no enqueued leg (whose frames overlap on the "
                     "library's render streams: their launches would enter a profiler's per-kernel average with stretched durations), no parity object, no CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed loop, write what its last step computed (rank 0: the RGBA8 back buffer, gathered when N > 1, and at N = 1 the composed "
+                    "RGBA32F image) as DIR/<name>.npy in float32, at most %d MB in all: an image larger than its share is a fixed, seeded sample of its pixels" % (DUMP_BYTES // 10**6))
     ap.add_argument("--watchdog", type=float, default=600.0, help="N > 1: seconds after which a rank that is still running dumps every thread's Python stack to stderr and exits with status 1 "
                     "(a collective whose peer never arrives cannot be left from inside the process; the launcher then stops the other ranks); 0 = off")
     return ap.parse_args()
@@ -129,6 +157,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
     # stdout carries ONE JSON line.  The library reports like the reference does ("Render buffer: WxH", rt64_view.cpp:150) with printf on
@@ -496,6 +526,17 @@ def main():
         assert s.accumFrames == stat_frames, (s.accumFrames, stat_frames)
         acc.update(trace=s.accumMsPrimaryTrace, shade=s.accumMsPrimaryShade, direct=s.accumMsDirect, indirect=s.accumMsIndirect, compose=s.accumMsComposePost,
                    build=s.accumMsBuild, total=s.accumMsTotal, denoise=s.accumMsDenoise, reflect=s.accumMsReflectRefract)
+    # What the last timed step handed its caller, read before any later leg draws again: rank 0's assembled frame when N > 1, else the
+    # device's back buffer and composed image.
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if native:
+            images = {"final_rgba8": host_frame.reshape(H, W, 4)}
+        elif G:
+            images = {"final_rgba8": gatherer.frame(last_slot).cpu().numpy().reshape(H, W, 4)}
+        else:
+            images = {"final_rgba8": scene.readback(rt64.IMAGE_FINAL_RGBA8), "output_rgba32f": scene.readback(rt64.IMAGE_OUTPUT_RGBA32F)}
+        dumped = dump_outputs(args.dump_outputs, images)
     # The reference uploads its tables and rebuilds the TLAS every frame (rt64_view.cpp:451 updateOnly = false, :1150-1152); the timed
     # loop above ran with the frame-table cache (identical descriptors are not re-uploaded).  Same K steps again with the cache off,
     # outside the timed region of `value`, so that the line carries both figures.
@@ -642,6 +683,8 @@ def main():
         if N > 1 and native and use_bands and rebalance_log:
             result["band_rebalance"] = rebalance_log
         result["prewarm_frames"] = args.prewarm
+        if dumped is not None:
+            result["dump_outputs"] = {"dir": args.dump_outputs, "step": "last timed step", "arrays": dumped}
         result["pass_events"] = "HIP events around every pass of every timed frame" if events_every == 1 else (
             "per-pass HIP events on every %dth timed frame (%d of %d frames sampled): each event is a barrier packet of ~5 us on the stream" % (events_every, stat_frames, args.steps))
         if args.option:

@@ -88,3 +88,28 @@ def test_gpus_flag_spawns_ranks_and_fails_loudly():
     assert r.returncode != 0 and '"n_gpus": 1' not in r.stdout
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=dict(env, WORLD_SIZE="1", RANK="0"), capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_are_float32_within_budget_and_sampled_the_same_way(bench, tmp_path):
+    """--dump-outputs: float32 .npy files, DUMP_BYTES at most in all; a 1080p back buffer stays whole, a 4K one and the 1080p composed image are
+    seeded samples of their pixels -- the same pixels on every run, so that two builds can be compared array for array."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    for (h, w) in ((1080, 1920), (2160, 3840)):
+        images = {"final_rgba8": rng.integers(0, 256, (h, w, 4), dtype=np.uint8), "output_rgba32f": rng.random((h, w, 4), dtype=np.float32)}
+        runs = []
+        for k in range(2):
+            d = tmp_path / ("%d_%d" % (h, k))
+            info = bench.dump_outputs(str(d), images)
+            arrays = {n: np.load(d / (n + ".npy")) for n in images}
+            assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_BYTES
+            assert all(a.dtype == np.float32 for a in arrays.values()) and set(info) == set(images)
+            runs.append(arrays)
+        for n in images:
+            assert np.array_equal(runs[0][n], runs[1][n]), n
+        fin, out = runs[0]["final_rgba8"], runs[0]["output_rgba32f"]
+        if h == 1080:
+            assert fin.shape == (h, w, 4) and np.array_equal(fin, images["final_rgba8"].astype(np.float32))
+        else:
+            assert fin.ndim == 2 and fin.shape[1] == 4 and set(np.unique(fin)) <= set(range(256))
+        assert out.ndim == 2 and out.shape[1] == 4 and np.isin(out[:, 0], images["output_rgba32f"][..., 0]).all()
