@@ -400,6 +400,8 @@ struct View {
     RasterPrologue prologue = {}; size_t prologueCopyBytes = 0;
     void flushTableCopy();
     void flushPrologue();
+    void discardPrologue();
+    void discardUpdate();
     std::vector<Texture *> usedTextures;
     // The frame tables live in ONE device allocation in their staging order (instances | textures | lights) so that a changed
     // frame costs one host-to-device copy (each copy packet is ~10 us of stream time, whatever its size).
@@ -955,6 +957,23 @@ void View::flushPrologue() {
     dev->workSinceMark = true;
 }
 
+// Work that View::update recorded as done (the slot's table bytes and BLAS key, a list's bytes and `ready`) but that a frame refused before flushPrologue never
+// queued: the keys are dropped with it, so that the next frame uploads and sets up again instead of rendering from a slot or a list that never received the work.
+void View::discardPrologue() {
+    if (prologueCopyBytes) { tab[tabCur].uploadedTables.clear(); tab[tabCur].cacheBlasKey.clear(); tab[tabCur].cacheImageValid = false; }
+    for (uint32_t i = 0; i < prologue.listCount; i++)
+        for (RasterList *rl : { &rasterBgEnv, &rasterBgScreen, &rasterFgScreen })
+            if (rl->table.ptr == prologue.list[i].deviceTable) { rl->ready = false; rl->uploaded.clear(); }
+    memset(&prologue, 0, sizeof(prologue)); prologueCopyBytes = 0;
+}
+// A frame refused half-way through View::update: besides the unqueued work, the texture slots it handed out (Texture::currentIndex) are still set -- the
+// next frame would take them for its own and leave those textures out of its table.
+void View::discardUpdate() {
+    for (Texture *t : usedTextures) t->currentIndex = -1;
+    usedTextures.clear();
+    discardPrologue();
+}
+
 void View::drawRasterList(RasterList &rl, uint8_t *target, bool clear) {
     if (!rl.ready || rl.triTotal == 0) return;
     Device *dev = scene->device;
@@ -1044,7 +1063,7 @@ static void host_build_tlas(const GpuInstance *inst, const float (*meshMin)[3], 
 
 void View::update() {                          // View::update, rt64_view.cpp:1053-1178
     Device *dev = scene->device;
-    memset(&prologue, 0, sizeof(prologue)); prologueCopyBytes = 0;       // (nothing is left from a frame that threw half-way)
+    discardPrologue();                         // (nothing is left from a frame that threw half-way; Device::draw has discarded it already)
     {   // View::createOutputBuffers: render size = lround(screen * resolutionScale) (rt64_view.cpp:138-139)
         const float scale = resolutionScale > 0.0f ? resolutionScale : 1.0f;
         int rw = std::max(1, (int)lroundf((float)dev->width * scale)), rh = std::max(1, (int)lroundf((float)dev->height * scale));
@@ -1286,6 +1305,7 @@ void View::update() {                          // View::update, rt64_view.cpp:10
         }
     }
     for (Texture *t : usedTextures) t->currentIndex = -1;
+    usedTextures.clear();                      // (a texture may be destroyed before the next frame: nothing keeps pointers to it)
 }
 
 void View::fillParams(FrameParams &P) {        // updateGlobalParamsBuffer, rt64_view.cpp:961-1028
@@ -1732,6 +1752,7 @@ void Device::draw(int, float) {                // Device::draw, rt64_device.cpp:
         // A frame the library refuses (or that fails half-way): the device keeps showing the last complete frame -- its stream and its back-buffer slot are current
         // again -- and whatever the failed frame has enqueued stays in order in front of everything that follows.
         if (cur != curBefore) { streamBusy[cur] = true; cur = curBefore; stream = streams[cur]; }
+        for (Scene *sc : scenes) for (View *v : sc->views) v->discardUpdate();
         try { joinStreams(); noteOrderedWork(); } catch (...) {}
         lastFramePure = false;
         for (Scene *sc : scenes) for (View *v : sc->views) v->img.final = finalOverride ? finalOverride : v->finalBuf[cur];

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_features import _variant, _rmse
+from test_gpu_features import _check, _variant, _rmse
 
 pytestmark = pytest.mark.gpu
 
@@ -376,3 +376,96 @@ def test_device_memory_comes_back_and_does_not_creep(rt64_lib, sample_data):
         t.draw(); t.close()
     after_all = _device_free_bytes()
     assert base - after_all <= (8 << 20), (before_all, base, after_all)
+
+
+W, H = 320, 180
+
+
+def _scene(rt64_lib, data):
+    from sm64rt_legacy_renderer_amd import sample_scene
+    return sample_scene.Rt64Scene(rt64_lib, data, W, H, hip_device=0)
+
+
+def _break_hud_stride(rt64_lib, s, k):
+    """RT64_SetMesh accepts any stride from 12 up; a raster mesh of 12-byte vertices is refused later, inside View::update (prepareRasterList), after the
+    frame's table upload and the background lists' setup have been recorded -- but before they are queued (flushPrologue)."""
+    pos = np.ascontiguousarray(s.data.meshes[k].vertices["position"][:, :3], dtype=np.float32)
+    idx = np.ascontiguousarray(s.data.meshes[k].indices, dtype=np.uint32)
+    rt64_lib.SetMesh(s.meshes[k], pos.ctypes.data, len(pos), 12, idx.ctypes.data, len(idx))
+
+
+def _moved(inst, x):
+    i = copy.copy(inst)
+    t = np.array(inst.transform, dtype=np.float32).copy(); t[3, 0] = np.float32(x)
+    i.transform = t; i.previous_transform = t
+    return i
+
+
+@pytest.mark.parametrize("frame_prologue", [1, 0])
+@pytest.mark.parametrize("host_tlas", [1, 0])
+def test_a_frame_refused_inside_update_leaves_no_stale_table_slot(rt64_lib, sample_data, frame_prologue, host_tlas):
+    """The refused frame moves the sphere: its tables get a slot and that slot's cache key, but the upload is lost with the frame.  The next frame
+    draws the same transform again -- it must upload again, not render from the slot, which still holds the tables of a frame TABLE_SLOTS (6) frames back."""
+    from sm64rt_legacy_renderer_amd import rt64
+    from oracle import oracle_py
+    data = _variant(sample_data, lambda d: None)
+    k = next(i for i, inst in enumerate(data.instances) if inst.name == "sphere")
+    hud = next(i.mesh for i in data.instances if i.name == "hudB")
+    s = _scene(rt64_lib, data)
+    o = oracle_py.OracleScene(data)
+    try:
+        assert s.option("frame_prologue", frame_prologue) and s.option("host_tlas", host_tlas)
+        s.option("count_traversal", 1)
+        for f in range(8):                                    # every table slot holds valid tables of an earlier sphere position
+            data.instances[k] = _moved(sample_data.instances[k], 0.25 * f)
+            s.draw()
+        data.instances[k] = _moved(sample_data.instances[k], -1.5)
+        _break_hud_stride(rt64_lib, s, hud)
+        s.draw()
+        assert "stride" in rt64_lib.last_error()
+        s.set_mesh(s.meshes[hud], data.meshes[hud].vertices, data.meshes[hud].indices)
+        s.draw()
+        o.set_instance(k, data.instances[k])
+        ref = o.render(W, H)
+        got = {n: s.readback(getattr(rt64, "IMAGE_" + n)) for n in ("OUTPUT_RGBA32F", "FINAL_RGBA8", "PRIMARY_HIT", "INSTANCE_ID")}
+        _check(got, ref, s.stats())          # hit records exact, composed images RMSE <= 1e-3, traversal counters exact
+    finally:
+        s.close(); o.close()
+
+
+def test_a_frame_refused_inside_update_leaves_no_stale_raster_list(rt64_lib, sample_data):
+    """The refused frame moves the background HUD (hudA) into another viewport: the setup of the back-buffer background list goes into the frame
+    prologue and is lost with the frame.  The next frame must set the list up again, not draw the records of the old viewport."""
+    from sm64rt_legacy_renderer_amd import rt64
+    from oracle import oracle_py
+    from test_gpu_raster import _final_close
+
+    def mod(d):
+        d.instances[1].viewport = (30, 20, 260, 140)         # the first ray-traced instance's rectangles: the background list is drawn on the back buffer too
+        d.instances[1].scissor = (50, 30, 200, 100)
+    data = _variant(sample_data, mod)
+    a = next(i for i, inst in enumerate(data.instances) if inst.name == "hudA")
+    hud = next(i.mesh for i in data.instances if i.name == "hudB")
+    s = _scene(rt64_lib, data)
+    try:
+        assert s.option("frame_prologue", 1)
+        for f in range(2):
+            s.draw()
+        moved = copy.copy(data.instances[a]); moved.viewport = (0, 0, 160, 90); moved.scissor = (0, 0, 120, 80)
+        data.instances[a] = moved
+        s.set_instance(a, moved)
+        _break_hud_stride(rt64_lib, s, hud)
+        s.draw()
+        assert "stride" in rt64_lib.last_error()
+        s.set_mesh(s.meshes[hud], data.meshes[hud].vertices, data.meshes[hud].indices)
+        s.draw()
+        got = {"FINAL_RGBA8": s.readback(rt64.IMAGE_FINAL_RGBA8)}
+    finally:
+        s.close()
+    o = oracle_py.OracleScene(data)
+    try:
+        ref = o.render(W, H)
+    finally:
+        o.close()
+    _final_close(got, ref)
+
