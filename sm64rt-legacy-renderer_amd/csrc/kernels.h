@@ -65,6 +65,11 @@ hipError_t launch_compose_post(const FrameParams &P, const ViewImages &I, int cu
 // perWave: frames without the LDS scene cache run one wave (an 8 x 8 wave-tile) per workgroup instead of one 16 x 16 tile
 hipError_t launch_lean_frame(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, bool perWave, hipStream_t s);
 hipError_t launch_post_process(const FrameParams &P, const ViewImages &I, hipStream_t s);      // PostProcessPS as its own pass (resolution scale / motion blur)
+// DebugPS in PostProcess's place (device option visualization_mode): the image the view shows, as RT64_ReadbackDevice selects it -- its storage
+// (kind: 0 raw 32-bit words, 1 half floats, 2 unorm8; srcBytes per pixel) and, for modes 1, 2 and 5, the frame tag of the reflection passes' state
+// (ViewImages::reflTag; 0: none) that a readback would fold back into the G-buffer first
+struct DebugSource { const void *ptr; int srcBytes, kind, mode; uint32_t reflTag; };
+hipError_t launch_debug_view(const FrameParams &P, const ViewImages &I, const DebugSource &src, hipStream_t s);
 // passes_simple.hip: the same launchers over kernels compiled without non-power-of-two texture addressing and without the shadow any-hit
 // program; the launchers above route to them when FrameParams::simpleKernels is set
 hipError_t launch_primary_shade_simple(const FrameParams &P, const ViewImages &I, const int32_t *hitInstance, int cur, bool transparentLighting, bool lean, hipStream_t s);

@@ -1691,16 +1691,22 @@ DEV f2 sample_flow_linear_wrap(const uint16_t *img, int w, int h, float u, float
     { const float top = c00.y + fx * (c10.y - c00.y), bot = c01.y + fx * (c11.y - c01.y); r.y = top + fy * (bot - top); }
     return r;
 }
+// Viewport + scissor of the full-screen triangle: the screen, or the rectangles of the first ray-traced instance (rt64_view.cpp:1258-1271,1624-1626).
+// False: pixel (x, y) of the back buffer is outside them; otherwise (u, v) is the FullScreenVS interpolant at the pixel centre.
+DEV bool full_screen_uv(PRef P, int x, int y, float &u, float &v) {
+    const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
+    if (x < P.rtScissor[0] || x >= P.rtScissor[2] || y < P.rtScissor[1] || y >= P.rtScissor[3]) return false;
+    if (!(cx >= P.rtViewport[0]) || !(cx < P.rtViewport[0] + P.rtViewport[2]) || !(cy >= P.rtViewport[1]) || !(cy < P.rtViewport[1] + P.rtViewport[3])) return false;
+    u = (cx - P.rtViewport[0]) / P.rtViewport[2]; v = (cy - P.rtViewport[1]) / P.rtViewport[3];
+    return true;
+}
 __global__ __launch_bounds__(256) void post_process_kernel(FrameParams Pv, ViewImages Iv) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
     const int sw = (int)P.resolution[2], sh = (int)P.resolution[3];
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= sw || y >= sh) return;
-    // viewport + scissor of the full-screen triangle: the screen, or the rectangles of the first ray-traced instance (rt64_view.cpp:1258-1271,1624-1626)
-    const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
-    if (x < P.rtScissor[0] || x >= P.rtScissor[2] || y < P.rtScissor[1] || y >= P.rtScissor[3]) return;
-    if (!(cx >= P.rtViewport[0]) || !(cx < P.rtViewport[0] + P.rtViewport[2]) || !(cy >= P.rtViewport[1]) || !(cy < P.rtViewport[1] + P.rtViewport[3])) return;
-    const float u = (cx - P.rtViewport[0]) / P.rtViewport[2], v = (cy - P.rtViewport[1]) / P.rtViewport[3];       // FullScreenVS interpolant at the pixel centre
+    float u, v;
+    if (!full_screen_uv(P, x, y, u, v)) return;
     f4 color; bool blurred = false;
     if (P.motionBlurStrength > 0.0f && P.motionBlurSamples > 0) {
         const f2 fl = sample_flow_linear_wrap(I.flow, P.width, P.height, u, v);
@@ -1722,6 +1728,82 @@ __global__ __launch_bounds__(256) void post_process_kernel(FrameParams Pv, ViewI
     }
     if (!blurred) color = sample_output_linear_wrap(P.postSource, P.postSourceW, P.postSourceH, u, v);
     store_rgba8(I.final, (size_t)y * (size_t)sw + x, color.x, color.y, color.z, 1.0f);
+}
+
+// One pixel of the debug view's image in its storage format (DebugSource::kind / srcBytes); single-channel images in .x, 32-bit words as their bits.
+DEV f4 debug_load(const DebugSource &src, size_t i) {
+    if (src.kind == 1) {
+        if (src.srcBytes == 8) return load_rgba16f(static_cast<const uint16_t *>(src.ptr), i);
+        const uint32_t h = static_cast<const uint32_t *>(src.ptr)[i];                                    // RG16F (flow)
+        return mk4(f16_bits_to_f32((uint16_t)(h & 0xFFFFu)), f16_bits_to_f32((uint16_t)(h >> 16)), 0.0f, 0.0f);
+    }
+    if (src.kind == 2) {
+        if (src.srcBytes == 4) return load_rgba8(static_cast<const uint8_t *>(src.ptr), i);
+        return mk4(from_unorm8(static_cast<const uint8_t *>(src.ptr)[i]), 0.0f, 0.0f, 0.0f);               // R8 masks
+    }
+    if (src.srcBytes == 16) { const float4 p = static_cast<const float4 *>(src.ptr)[i]; return mk4(p.x, p.y, p.z, p.w); }
+    return mk4(__uint_as_float(static_cast<const uint32_t *>(src.ptr)[i]), 0.0f, 0.0f, 0.0f);           // instance id / depth
+}
+// DebugPS.hlsl:47-157 in PostProcess's place (device option visualization_mode; rt64_view.cpp:1628-1650): the texel uint2(uv * resolution.xy) of the image the mode
+// names -- nearest, zeros out of range -- shown as DebugPS shows it and blended over the back buffer the background pass left (alphaBlendDesc, rt64_device.cpp:532-538:
+// SRC_ALPHA / INV_SRC_ALPHA, alpha ONE / INV_SRC_ALPHA, the source clamped to [0, 1] like a UNORM target clamps it).  The mode is uniform over the launch.
+__global__ __launch_bounds__(256) void debug_view_kernel(FrameParams Pv, ViewImages Iv, DebugSource src) {
+    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv;
+    const int sw = (int)P.resolution[2], sh = (int)P.resolution[3];
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= sw || y >= sh) return;
+    if (!P.separatePost && (y < P.tileY0 || y >= P.tileY1 || !row_owned(P, y))) return;     // back-buffer rows are render rows: this device's only
+    float u, v;
+    if (!full_screen_uv(P, x, y, u, v)) return;
+    const float px = u * P.resolution[0], py = v * P.resolution[1];
+    const uint32_t w = (uint32_t)P.width, h = (uint32_t)P.height;
+    auto texel = [&](uint32_t tx, uint32_t ty) { return tx < w && ty < h ? debug_load(src, (size_t)ty * w + tx) : mk4(0.0f, 0.0f, 0.0f, 0.0f); };
+    f4 c;
+    if (src.mode == RT64_IMAGE_FLOW) {
+        // getMotionVector: a 1-pixel line from the centre of the pixel's 32 x 32 block along the flow found there (distanceFromLineSegment < 1)
+        const float sx = floorf(px / 32.0f) * 32.0f + 16.0f, sy = floorf(py / 32.0f) * 32.0f + 16.0f;
+        const f4 fl = texel((uint32_t)rintf(sx), (uint32_t)rintf(sy));
+        const float ex = sx + fl.x, ey = sy + fl.y;
+        const float len = sqrtf((sx - ex) * (sx - ex) + (sy - ey) * (sy - ey)), l2 = len * len;
+        float dist;
+        if (l2 == 0.0f) dist = sqrtf((px - sx) * (px - sx) + (py - sy) * (py - sy));
+        else {
+            const float t = fmaxf(0.0f, fminf(1.0f, ((px - sx) * (ex - sx) + (py - sy) * (ey - sy)) / l2));
+            const float qx = sx + t * (ex - sx), qy = sy + t * (ey - sy);
+            dist = sqrtf((px - qx) * (px - qx) + (py - qy) * (py - qy));
+        }
+        c = dist < 1.0f ? mk4(1.0f, 1.0f, 1.0f, 1.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    else {
+        const uint32_t tx = (uint32_t)px, ty = (uint32_t)py;
+        c = texel(tx, ty);
+        // the G-buffer after the reflection passes: their continuation state where they tagged the pixel (apply_reflection_state_kernel, without the write)
+        if (src.reflTag && tx < w && ty < h && I.reflTag[(size_t)ty * w + tx] == src.reflTag) {
+            const size_t i = (size_t)ty * w + tx;
+            const uint4 s0 = I.reflState0[i], s1 = I.reflState1[i];
+            if (src.mode == RT64_IMAGE_SHADING_POSITION) c = mk4(__uint_as_float(s0.x), __uint_as_float(s0.y), __uint_as_float(s0.z), 0.0f);
+            else if (src.mode == RT64_IMAGE_SHADING_NORMAL) c = unpack_rgba16f_bits(s1.z, s1.w);
+            else c.x = __uint_as_float(s0.w);
+        }
+        switch (src.mode) {
+        case RT64_IMAGE_SHADING_NORMAL: c = mk4((c.x + 1.0f) / 2.0f, (c.y + 1.0f) / 2.0f, (c.z + 1.0f) / 2.0f, 1.0f); break;
+        case RT64_IMAGE_INSTANCE_ID: {          // getInstanceId: a colour per instance, nothing on a miss
+            const int32_t id = (int32_t)__float_as_uint(c.x);
+            if (id < 0) { c = mk4(0.0f, 0.0f, 0.0f, 0.0f); break; }
+            uint32_t seed = init_rand((uint32_t)id, 0, 16);
+            const float r = next_rand(seed), g = next_rand(seed), b = next_rand(seed);
+            c = mk4(r, g, b, 1.0f);
+            break;
+        }
+        case RT64_IMAGE_REACTIVE_MASK: case RT64_IMAGE_LOCK_MASK: case RT64_IMAGE_DEPTH: c = mk4(c.x, c.x, c.x, 1.0f); break;
+        default: c.w = 1.0f;
+        }
+    }
+    auto unorm = [](float a) { return a > 0.0f ? fminf(a, 1.0f) : 0.0f; };
+    const float r = unorm(c.x), g = unorm(c.y), b = unorm(c.z), a = unorm(c.w), ia = 1.0f - a;
+    const size_t i = (size_t)y * (size_t)sw + x;
+    const f4 d = load_rgba8(I.final, i);
+    store_rgba8(I.final, i, r * a + d.x * ia, g * a + d.y * ia, b * a + d.z * ia, a + d.w * ia);
 }
 
 // IndirectRayGen with giSamples == 0 (IndirectRayGen.hlsl:135): every pixel gets ambientBase + ambientNoGI, history 0.
@@ -1946,6 +2028,11 @@ hipError_t launch_spp_accumulate(const FrameParams &P, const ViewImages &I, floa
 hipError_t launch_post_process(const FrameParams &P, const ViewImages &I, hipStream_t s) {
     dim3 grid((unsigned)((int)P.resolution[2] + 31) / 32, (unsigned)((int)P.resolution[3] + 7) / 8);
     hipLaunchKernelGGL(post_process_kernel, grid, dim3(256), 0, s, P, I);
+    return hipGetLastError();
+}
+hipError_t launch_debug_view(const FrameParams &P, const ViewImages &I, const DebugSource &src, hipStream_t s) {
+    dim3 grid((unsigned)((int)P.resolution[2] + 31) / 32, (unsigned)((int)P.resolution[3] + 7) / 8);
+    hipLaunchKernelGGL(debug_view_kernel, grid, dim3(256), 0, s, P, I, src);
     return hipGetLastError();
 }
 __global__ __launch_bounds__(256) void stack_slab_init_kernel(uint32_t *slab, size_t lanes, const uint32_t *flag) {

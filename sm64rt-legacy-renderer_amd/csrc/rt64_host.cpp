@@ -164,6 +164,8 @@ struct Options {
     bool haloDryRun = false;       // timing aid: an exchanging band runs its frame but moves no halo rows (what one rank's GPU work costs, measured on one device; results outside the band's interior are then wrong)
     int haloMargin = SVGF_INPUT_HALO_ROWS;   // with a halo exchange: rows of G-buffer + GI kept around the band (temporal history under camera motion); at least SVGF_INPUT_HALO_ROWS
     int maxReflections = 2;        // rt64_view.cpp:60 (inspector-only knob in the reference)
+    uint32_t motionBlurSamples = 32;   // rt64_view.cpp:53, PostProcessPS.hlsl:14-33 taps (inspector-only knob in the reference; 0: no blur)
+    int visualizationMode = 0;     // rt64_inspector.cpp:196-205: 0 the frame, 1..16 DebugPS's view of image RT64_IMAGE_* = mode in PostProcess's place (View::render)
     // Path-tracing extensions beyond the reference (one bounce per GI ray, IndirectRayGen.hlsl:58-131; one primary sample per pixel, rt64.h:172-182); DESIGN.md 4:
     int giBounces = 1;             // 2: a GI ray that resolves to a surface sends a second cosine-weighted ray from there; what it finds stands where the constant ambient term stands at the first hit
     int primarySpp = 1;            // N: RT64_DrawDevice renders N jittered sub-frames (every pass up to Compose each) and presents the mean of their composed outputs
@@ -359,7 +361,7 @@ struct RenderInstance { Instance *instance; };
 struct View {
     Scene *scene;
     // RT64_VIEW_DESC state + inspector-only knobs, defaults of rt64_view.cpp:47-66
-    float resolutionScale = 1.0f, motionBlurStrength = 0.0f; uint32_t diSamples = 0, giSamples = 0, maxLights = 12, motionBlurSamples = 32;
+    float resolutionScale = 1.0f, motionBlurStrength = 0.0f; uint32_t diSamples = 0, giSamples = 0, maxLights = 12;
     bool denoiserEnabled = false;
     // RT64_VIEW_DESC.upscaler / upscalerMode: AUTO and FSR select the built-in temporal upscaler (upscale.hip); the vendor SDKs do not exist here
     int upscaler = RT64_UPSCALER_OFF, upscalerMode = RT64_UPSCALER_MODE_AUTO; float upscalerSharpness = 0.0f;
@@ -376,7 +378,7 @@ struct View {
     float rtViewport[4] = { 0, 0, 0, 0 }; int rtScissor[4] = { 0, 0, 0, 0 }; bool rtRect = false;
     bool needSpillSlab = false;                // some walk of this frame can outgrow its LDS stack entries (see View::update)
     uint32_t cacheWords = 0;                   // LDS scene cache size in 16-byte words (0: the scene does not fit / option lds_cache = 0)
-    bool separatePost() const { return upscaleActive || rtRect || imgW != finalW || imgH != finalH || (motionBlurStrength > 0.0f && motionBlurSamples > 0); }
+    bool separatePost() const { return upscaleActive || rtRect || imgW != finalW || imgH != finalH || (motionBlurStrength > 0.0f && scene->device->opt.motionBlurSamples > 0); }
     // device images
     ViewImages img = {};
     std::vector<void *> allocations; uint32_t bounceSamples = 0;
@@ -1290,7 +1292,7 @@ void View::update() {                          // View::update, rt64_view.cpp:10
         const bool whole = separatePost();                     // the back buffer is screen size; device rows are screen rows
         const int sy0 = whole ? 0 : dev->tileY0, sy1 = whole ? finalH : dev->tileY1;
         prepareRasterList(rasterBg, rasterBgEnv, finalW, finalH, 0, finalH, false);               // gBackground: every rank needs all of it (env-map lookups)
-        prepareRasterList((rtInstances.empty() || rtRect) ? rasterBg : std::vector<RenderInstance>(), rasterBgScreen, finalW, finalH, sy0, sy1, true);
+        prepareRasterList((rtInstances.empty() || rtRect || dev->opt.visualizationMode != 0) ? rasterBg : std::vector<RenderInstance>(), rasterBgScreen, finalW, finalH, sy0, sy1, true);
         prepareRasterList(rasterFg, rasterFgScreen, finalW, finalH, sy0, sy1, true);
         flushPrologue();
         if (!rasterBg.empty() && (backgroundW != finalW || backgroundH != finalH)) { background.reserve((size_t)finalW * finalH * 4); backgroundW = finalW; backgroundH = finalH; rasterBgEnv.changed = true; }      // (a resize has dropped every kept frame: View::createImages)
@@ -1346,7 +1348,7 @@ void View::fillParams(FrameParams &P) {        // updateGlobalParamsBuffer, rt64
     if (upscaleActive) { const int fi = (int)(frameCount % (uint32_t)jitterPhases) + 1; pixelJitter[0] = halton_sequence(fi, 2) - 0.5f; pixelJitter[1] = halton_sequence(fi, 3) - 0.5f; }
     if (subFrames > 1) { pixelJitter[0] = halton_sequence(subFrame + 1, 2) - 0.5f; pixelJitter[1] = halton_sequence(subFrame + 1, 3) - 0.5f; }      // P2
     P.pixelJitter[0] = pixelJitter[0]; P.pixelJitter[1] = pixelJitter[1];
-    P.motionBlurStrength = motionBlurStrength; P.motionBlurSamples = motionBlurSamples;
+    P.motionBlurStrength = motionBlurStrength; P.motionBlurSamples = dev->opt.motionBlurSamples;
     P.skyPlaneTexIndex = skyPlane ? 0 : -1;
     P.skyTiled = nullptr; P.skyTiledLog2W = P.skyTiledLog2H = 0;
     // the tiled copy only pays for random lookups (bounce / reflection rays): frames without GI or reflections never make them
@@ -1416,6 +1418,36 @@ void View::fillParams(FrameParams &P) {        // updateGlobalParamsBuffer, rt64
     if (dev->opt.tileTiming) { dev->tileTiming.reserve((size_t)RT_TIMING_WAVES * 3); P.tileTiming = dev->tileTiming.ptr; }      // two records per wave + one more in diagnostic builds
 }
 
+struct ImageInfo { const void *ptr; int srcBytes; int channels; int kind; };   // kind: 0 raw copy, 1 half->float, 2 unorm8->float
+
+// Where image `image` of a frame lives and how it is stored.  cur: the frame's set of the double-buffered images (View::render's `cur`).
+static bool image_info(const ViewImages &I, int cur, int image, ImageInfo &info, size_t &dstPixelBytes) {
+    switch (image) {
+    case RT64_IMAGE_FINAL_RGBA8: info = { I.final, 4, 4, 0 }; dstPixelBytes = 4; return true;
+    case RT64_IMAGE_SHADING_POSITION: info = { I.shadingPosition, 16, 4, 0 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_SHADING_NORMAL: info = { I.shadingNormal, 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_SHADING_SPECULAR: info = { I.shadingSpecular, 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_DIFFUSE: info = { I.diffuse, 4, 4, 2 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_INSTANCE_ID: info = { I.instanceId, 4, 1, 0 }; dstPixelBytes = 4; return true;
+    case RT64_IMAGE_FIRST_INSTANCE_ID: info = { I.firstInstanceId, 4, 1, 0 }; dstPixelBytes = 4; return true;
+    case RT64_IMAGE_DIRECT_LIGHT_RAW: info = { I.directLight[cur], 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_DIRECT_LIGHT_FILTERED: info = { I.filteredDirect[1], 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_INDIRECT_LIGHT_RAW: info = { I.indirectLight[cur], 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_INDIRECT_LIGHT_FILTERED: info = { I.filteredIndirect[1], 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_REFLECTION: info = { I.reflection, 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_REFRACTION: info = { I.refraction, 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_TRANSPARENT: info = { I.transparent, 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_VIEW_DIRECTION: info = { I.viewDirection, 8, 4, 1 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_FLOW: info = { I.flow, 4, 2, 1 }; dstPixelBytes = 8; return true;
+    case RT64_IMAGE_REACTIVE_MASK: info = { I.reactiveMask, 1, 1, 2 }; dstPixelBytes = 4; return true;
+    case RT64_IMAGE_LOCK_MASK: info = { I.lockMask, 1, 1, 2 }; dstPixelBytes = 4; return true;
+    case RT64_IMAGE_DEPTH: info = { I.depth[cur], 4, 1, 0 }; dstPixelBytes = 4; return true;
+    case RT64_IMAGE_OUTPUT_RGBA32F: info = { I.output, 16, 4, 0 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_PRIMARY_HIT: info = { I.primaryHit, 16, 4, 0 }; dstPixelBytes = 16; return true;
+    default: return false;
+    }
+}
+
 static void halo_exchange(Device *dev, const ViewImages &img, int W, int H, hipStream_t s);     // (after Gather, below)
 
 void View::render() {                          // View::render, rt64_view.cpp:1180-1670
@@ -1437,10 +1469,13 @@ void View::render() {                          // View::render, rt64_view.cpp:11
     };
     auto L = [&](hipError_t e) { HIP_CHECK(e); dev->workSinceMark = true; };       // a launch between two marks
     if (!perspectiveSet) throw std::runtime_error("RT64_DrawDevice: RT64_SetViewPerspective was never called (fov must be > 0).");
+    // The flow view draws a row's line from the flow at its block's centre row, which another device of the partition may own.
+    const int debugMode = dev->opt.visualizationMode;
+    if (debugMode == RT64_IMAGE_FLOW && dev->ownedRows() < dev->height) throw std::runtime_error("RT64_DrawDevice: visualization_mode 13 (flow) is not drawn on a partitioned device.");
     // Lean frame: nothing downstream reads the view direction, the reflection / refraction / transparent accumulators, motion
     // vectors, upscaler masks, history guides or a GI buffer.  A full frame after lean ones reads the previous frame's guides and
     // history (temporal reprojection), so what that lean frame skipped is produced first, while its hit records still exist.
-    const bool leanNow = !rtInstances.empty() && dev->opt.leanFrames && !upscaleActive && !anyNonOpaque && !anyReflection && !anyRefraction && !anyFog && giSamples == 0 && motionBlurStrength <= 0.0f && dev->leanHoldoff == 0 && subFrames == 1;
+    const bool leanNow = !rtInstances.empty() && dev->opt.leanFrames && !upscaleActive && !anyNonOpaque && !anyReflection && !anyRefraction && !anyFog && giSamples == 0 && motionBlurStrength <= 0.0f && dev->leanHoldoff == 0 && subFrames == 1 && debugMode == 0;
     if (leanFrame && !leanNow) materialise();
     if (subFrames > 1 && (upscaleActive || rtRect || separatePost())) throw std::runtime_error("RT64_DrawDevice: primary_spp > 1 is not combined with an upscaler, a resolution scale, motion blur or a viewport rectangle.");
     FrameParams P;
@@ -1506,7 +1541,7 @@ void View::render() {                          // View::render, rt64_view.cpp:11
         const bool fused = lean && dev->opt.fusedLean;
         // The same one-kernel form serves full frames whose instances are all provably opaque (GI / denoiser / reflection frames):
         // it then writes the whole G-buffer over the rows with the denoiser halo (X) and DirectRayGen's images over the owned rows.
-        const bool fusedFull = !lean && !klist && dev->opt.fusedLean;
+        const bool fusedFull = !lean && !klist && dev->opt.fusedLean && debugMode == 0;      // (a debug view is drawn from frames of the separate kernels: never fused)
         leanFrame = lean; fusedFrame = fused; fusedFullFrame = fusedFull; lastParams = P; lastCur = cur;
         // Only the one-kernel lean frame that stores nothing but its slot's back buffer may run beside its neighbours (Device::streams); every other kind of
         // frame reads or writes images that are not per slot and runs behind everything enqueued before it.
@@ -1656,7 +1691,20 @@ void View::render() {                          // View::render, rt64_view.cpp:11
             P.postSource = upscaled[upSwap]; P.postSourceW = finalW; P.postSourceH = finalH;
             upValid = true; upSwap ^= 1;
         }
-        if (P.separatePost) L(launch_post_process(P, img, s));
+        if (debugMode != 0 && subFrame == subFrames - 1) {
+            // DebugPS in PostProcess's place (rt64_view.cpp:1628-1650), blended over the cleared buffer + background instances (those are already there around a viewport
+            // rectangle); it shows the image RT64_ReadbackDevice returns for this frame, the G-buffer after the reflection passes included
+            if (!rtRect) {
+                L(launch_clear_final(P, img, s));
+                drawRasterList(rasterBgScreen, img.final);
+            }
+            ImageInfo info; size_t pixelBytes;
+            image_info(img, cur, debugMode, info, pixelBytes);
+            const bool reflected = reflStatePending && (debugMode == RT64_IMAGE_SHADING_POSITION || debugMode == RT64_IMAGE_SHADING_NORMAL || debugMode == RT64_IMAGE_INSTANCE_ID);
+            const DebugSource src = { info.ptr, info.srcBytes, info.kind, debugMode, reflected ? reflStateTag : 0u };
+            L(launch_debug_view(P, img, src, s));
+        }
+        else if (P.separatePost) L(launch_post_process(P, img, s));
     }
     else {
         dev->impure();
@@ -1868,37 +1916,6 @@ static float half_to_float(uint16_t h) {
     float f; memcpy(&f, &bits, 4); return f;
 }
 
-struct ImageInfo { const void *ptr; int srcBytes; int channels; int kind; };   // kind: 0 raw copy, 1 half->float, 2 unorm8->float
-
-static bool image_info(View *v, int image, ImageInfo &info, size_t &dstPixelBytes) {
-    const ViewImages &I = v->img;
-    const int cur = v->rtSwap ? 0 : 1;        // rtSwap was flipped at the end of the frame: the last rendered set is the other one
-    switch (image) {
-    case RT64_IMAGE_FINAL_RGBA8: info = { I.final, 4, 4, 0 }; dstPixelBytes = 4; return true;
-    case RT64_IMAGE_SHADING_POSITION: info = { I.shadingPosition, 16, 4, 0 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_SHADING_NORMAL: info = { I.shadingNormal, 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_SHADING_SPECULAR: info = { I.shadingSpecular, 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_DIFFUSE: info = { I.diffuse, 4, 4, 2 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_INSTANCE_ID: info = { I.instanceId, 4, 1, 0 }; dstPixelBytes = 4; return true;
-    case RT64_IMAGE_FIRST_INSTANCE_ID: info = { I.firstInstanceId, 4, 1, 0 }; dstPixelBytes = 4; return true;
-    case RT64_IMAGE_DIRECT_LIGHT_RAW: info = { I.directLight[cur], 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_DIRECT_LIGHT_FILTERED: info = { I.filteredDirect[1], 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_INDIRECT_LIGHT_RAW: info = { I.indirectLight[cur], 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_INDIRECT_LIGHT_FILTERED: info = { I.filteredIndirect[1], 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_REFLECTION: info = { I.reflection, 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_REFRACTION: info = { I.refraction, 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_TRANSPARENT: info = { I.transparent, 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_VIEW_DIRECTION: info = { I.viewDirection, 8, 4, 1 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_FLOW: info = { I.flow, 4, 2, 1 }; dstPixelBytes = 8; return true;
-    case RT64_IMAGE_REACTIVE_MASK: info = { I.reactiveMask, 1, 1, 2 }; dstPixelBytes = 4; return true;
-    case RT64_IMAGE_LOCK_MASK: info = { I.lockMask, 1, 1, 2 }; dstPixelBytes = 4; return true;
-    case RT64_IMAGE_DEPTH: info = { I.depth[cur], 4, 1, 0 }; dstPixelBytes = 4; return true;
-    case RT64_IMAGE_OUTPUT_RGBA32F: info = { I.output, 16, 4, 0 }; dstPixelBytes = 16; return true;
-    case RT64_IMAGE_PRIMARY_HIT: info = { I.primaryHit, 16, 4, 0 }; dstPixelBytes = 16; return true;
-    default: return false;
-    }
-}
-
 static View *first_view(Device *dev) { for (Scene *sc : dev->scenes) for (View *v : sc->views) return v; return nullptr; }
 
 static size_t readback(Device *dev, int image, void *dst, size_t dstBytes, bool toDevice) {
@@ -1932,7 +1949,8 @@ static size_t readback(Device *dev, int image, void *dst, size_t dstBytes, bool 
     if (image != RT64_IMAGE_FINAL_RGBA8 && (image != RT64_IMAGE_OUTPUT_RGBA32F || v->fusedFrame)) v->materialise();
     if (image == RT64_IMAGE_SHADING_POSITION || image == RT64_IMAGE_VIEW_DIRECTION || image == RT64_IMAGE_SHADING_NORMAL || image == RT64_IMAGE_INSTANCE_ID) v->applyReflectionState();
     ImageInfo info; size_t dstPixelBytes;
-    if (!image_info(v, image, info, dstPixelBytes)) throw std::runtime_error("RT64_ReadbackDevice: unknown image id.");
+    // rtSwap was flipped at the end of the frame: the last rendered set is the other one
+    if (!image_info(v->img, v->rtSwap ? 0 : 1, image, info, dstPixelBytes)) throw std::runtime_error("RT64_ReadbackDevice: unknown image id.");
     // Sizes: every image has the render size except the back buffer (screen size); they differ only with resolutionScale != 1,
     // which renders the whole frame on this device.
     const bool isFinal = image == RT64_IMAGE_FINAL_RGBA8, scaled = v->imgW != v->finalW || v->imgH != v->finalH;
@@ -2084,6 +2102,8 @@ RT64_EXPORT int RT64_SetDeviceOption(RT64_DEVICE *device, const char *key, doubl
     else if (k == "lean_frames") d->opt.leanFrames = value != 0.0;                // 0: always write every image of the reference's G-buffer
     else if (k == "always_rebuild") d->opt.alwaysRebuild = value != 0.0;          // upload tables + rebuild the TLAS every frame like the reference
     else if (k == "max_reflections") d->opt.maxReflections = std::max(0, (int)value);
+    else if (k == "motion_blur_samples") { if (!(value >= 0.0 && value <= 1024.0) || value != std::floor(value)) return 0; d->opt.motionBlurSamples = (uint32_t)value; }      // (the blur loops once per sample on every pixel)
+    else if (k == "visualization_mode") { if (!(value >= 0.0 && value <= 16.0) || value != std::floor(value)) return 0; d->opt.visualizationMode = (int)value; }
     else if (k == "gi_bounces") { if (value != 1.0 && value != 2.0) return 0; d->opt.giBounces = (int)value; }
     else if (k == "primary_spp") { if (!(value >= 1.0 && value <= 64.0)) return 0; d->opt.primarySpp = (int)value; }
     else if (k == "max_frame_groups") d->opt.maxFrameGroups = value >= 1.0 && value <= (double)RT_MAX_FRAME_GROUPS ? (unsigned)value : RT_MAX_FRAME_GROUPS;
