@@ -35,6 +35,13 @@ hipError_t lbvh_launch_batch(const LbvhArgs *deviceArgs, uint32_t count, uint32_
 hipError_t tile_texture_launch(const uint8_t *rgba, uint32_t *tiled, uint32_t width, uint32_t height, hipStream_t stream);
 hipError_t bc7_decode_launch(const uint8_t *blocks, uint8_t *rgba, uint32_t width, uint32_t height, hipStream_t stream);
 
+// ---- mipgen.hip ---------------------------------------------------------------------------------------------------
+// Mip chain of an RGBA8 texture (device option generate_mipmaps; rules M1-M6 in mipgen.hip): level 0 is in place at mipOffset[0], the
+// launches make levels 1 .. levels - 1.  A chain whose level 1 holds at most MIPGEN_TAIL_TEXELS texels is one launch of one workgroup.
+#define MIPGEN_TAIL_TEXELS 4096u
+int mipgen_level_count(int width, int height);       // M2: min(floor(log2(max(w, h))) + 1, RT64_MAX_MIPS)
+hipError_t mipgen_launch(uint8_t *texels, const uint32_t *mipOffset, uint32_t width, uint32_t height, int levels, hipStream_t stream);
+
 // ---- passes.hip ---------------------------------------------------------------------------------------------------
 #define RT_CACHE_MAX_WORDS 1536       // LDS scene cache, nodes + instance records: at most 24 KB next to the 8 KB stack (int16 entries) and the light columns of a workgroup, four workgroups per CU
 #define RT_STACK_LDS 24               // traversal stack entries per lane in LDS of the kernels without the scene cache; deeper levels go to the HBM spill slab

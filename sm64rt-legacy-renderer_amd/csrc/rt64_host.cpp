@@ -166,6 +166,7 @@ struct Options {
     int maxReflections = 2;        // rt64_view.cpp:60 (inspector-only knob in the reference)
     uint32_t motionBlurSamples = 32;   // rt64_view.cpp:53, PostProcessPS.hlsl:14-33 taps (inspector-only knob in the reference; 0: no blur)
     int visualizationMode = 0;     // rt64_inspector.cpp:196-205: 0 the frame, 1..16 DebugPS's view of image RT64_IMAGE_* = mode in PostProcess's place (View::render)
+    bool generateMipmaps = false;  // RGBA8 textures created while it is set get a full mip chain (rt64_texture.cpp:38, 216; rules M1-M6 in mipgen.hip)
     // Path-tracing extensions beyond the reference (one bounce per GI ray, IndirectRayGen.hlsl:58-131; one primary sample per pixel, rt64.h:172-182); DESIGN.md 4:
     int giBounces = 1;             // 2: a GI ray that resolves to a surface sends a second cosine-weighted ray from there; what it finds stands where the constant ambient term stands at the first hit
     int primarySpp = 1;            // N: RT64_DrawDevice renders N jittered sub-frames (every pass up to Compose each) and presents the mean of their composed outputs
@@ -535,8 +536,11 @@ Device::~Device() {
 void Texture::setRGBA8(const void *bytes, int byteCount, int w, int h, int rowPitch) {
     if (!bytes || w <= 0 || h <= 0 || rowPitch < w * 4 || (long long)rowPitch * h > (long long)byteCount + (rowPitch - w * 4)) throw std::runtime_error("RT64_CreateTexture: invalid RGBA8 description.");
     device->enter();
-    width = w; height = h; mips = 1; mipOffset[0] = 0;     // mip generation is compiled out in the reference (rt64_device.cpp:758-762)
-    texels.reserve((size_t)w * h * 4);
+    // One level unless generate_mipmaps is set (mip generation is compiled out in the reference, rt64_device.cpp:758-762); M2 otherwise
+    width = w; height = h; mips = device->opt.generateMipmaps ? mipgen_level_count(w, h) : 1;
+    size_t totalTexels = 0;
+    for (int m = 0; m < mips; m++) { mipOffset[m] = (uint32_t)totalTexels; totalTexels += (size_t)std::max(w >> m, 1) * std::max(h >> m, 1); }
+    texels.reserve(totalTexels * 4);
     uint8_t *stage = static_cast<uint8_t *>(device->staging((size_t)w * h * 4));
     uint8_t mn = 255, mx = 0;
     for (int y = 0; y < h; y++) {
@@ -546,6 +550,7 @@ void Texture::setRGBA8(const void *bytes, int byteCount, int w, int h, int rowPi
     }
     minAlpha = mn; maxAlpha = mx;
     HIP_CHECK(hipMemcpyAsync(texels.ptr, stage, (size_t)w * h * 4, hipMemcpyHostToDevice, device->stream));
+    if (mips > 1) HIP_CHECK(mipgen_launch(texels.ptr, mipOffset, (uint32_t)w, (uint32_t)h, mips, device->stream));      // minAlpha / maxAlpha hold for every level (M5)
     HIP_CHECK(hipStreamSynchronize(device->stream));        // the reference submits + waits per texture (rt64_texture.cpp:130-137)
 }
 
@@ -2104,6 +2109,7 @@ RT64_EXPORT int RT64_SetDeviceOption(RT64_DEVICE *device, const char *key, doubl
     else if (k == "max_reflections") d->opt.maxReflections = std::max(0, (int)value);
     else if (k == "motion_blur_samples") { if (!(value >= 0.0 && value <= 1024.0) || value != std::floor(value)) return 0; d->opt.motionBlurSamples = (uint32_t)value; }      // (the blur loops once per sample on every pixel)
     else if (k == "visualization_mode") { if (!(value >= 0.0 && value <= 16.0) || value != std::floor(value)) return 0; d->opt.visualizationMode = (int)value; }
+    else if (k == "generate_mipmaps") { if (value != 0.0 && value != 1.0) return 0; d->opt.generateMipmaps = value != 0.0; }      // applies to RGBA8 textures created from now on (M1)
     else if (k == "gi_bounces") { if (value != 1.0 && value != 2.0) return 0; d->opt.giBounces = (int)value; }
     else if (k == "primary_spp") { if (!(value >= 1.0 && value <= 64.0)) return 0; d->opt.primarySpp = (int)value; }
     else if (k == "max_frame_groups") d->opt.maxFrameGroups = value >= 1.0 && value <= (double)RT_MAX_FRAME_GROUPS ? (unsigned)value : RT_MAX_FRAME_GROUPS;

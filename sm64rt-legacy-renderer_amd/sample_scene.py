@@ -324,11 +324,18 @@ def apply_bench_config(data: "SceneData", config: str):
 class Rt64Scene:
     """Drives librt64.so with a SceneData exactly like the sample drives rt64lib.dll."""
 
-    def __init__(self, lib: rt64.Library, data: SceneData, width: int, height: int, hip_device: int = -1):
+    def __init__(self, lib: rt64.Library, data: SceneData, width: int, height: int, hip_device: int = -1, options=None):
+        """options: {key: value} device options set right after the device is created, before any texture or mesh exists (generate_mipmaps
+        only applies to textures created while it is set); a refused option raises."""
         self.lib, self.data, self.width, self.height = lib, data, width, height
         self.device = lib.CreateDeviceHeadless(width, height, hip_device)
         if not self.device:
             raise RuntimeError("RT64_CreateDeviceHeadless failed: " + lib.last_error())
+        for k, v in (options or {}).items():
+            if not self.option(k, v):
+                lib.DestroyDevice(self.device)
+                self.device = None
+                raise ValueError("RT64_SetDeviceOption(%s, %r) refused" % (k, v))
         self.scene = lib.CreateScene(self.device)
         lib.SetSceneDescription(self.scene, data.desc)
         self.shader = lib.CreateShader(self.device, data.shader_id, data.shader_filter, data.shader_haddr, data.shader_vaddr, data.shader_flags)
