@@ -101,6 +101,10 @@ enum { /* ref:70-86 */
     RT64_UPSCALER_MODE_AUTO = 0x0, RT64_UPSCALER_MODE_ULTRA_PERFORMANCE = 0x1, RT64_UPSCALER_MODE_PERFORMANCE = 0x2,
     RT64_UPSCALER_MODE_BALANCED = 0x3, RT64_UPSCALER_MODE_QUALITY = 0x4, RT64_UPSCALER_MODE_ULTRA_QUALITY = 0x5,
     RT64_UPSCALER_MODE_NATIVE = 0x6,
+    /* RT64_TEXTURE_FORMAT_DDS accepts (DX10 dxgiFormat / legacy FourCC / legacy 32-bit RGB masks): BC1 (71, 72 / DXT1), BC2 (74, 75 / DXT2, DXT3),
+       BC3 (77, 78 / DXT4, DXT5), BC4_UNORM (80 / ATI1, BC4U), BC5_UNORM (83 / ATI2, BC5U), BC7 (98, 99), R8G8B8A8 (28, 29 / R mask 0xff),
+       B8G8R8A8 (87, 91 / masks 0xff0000, 0xff00, 0xff, 0xff000000), B8G8R8X8 (88, 93 / the same with A = 0).  Every format is decoded to RGBA8 once
+       at creation (rules D1-D7; _SRGB texels are kept as stored); SNORM, BC6H, typeless and other formats are refused. */
     RT64_TEXTURE_FORMAT_RGBA8 = 0x1, RT64_TEXTURE_FORMAT_DDS = 0x2
 };
 

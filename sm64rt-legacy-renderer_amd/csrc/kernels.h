@@ -35,6 +35,14 @@ hipError_t lbvh_launch_batch(const LbvhArgs *deviceArgs, uint32_t count, uint32_
 hipError_t tile_texture_launch(const uint8_t *rgba, uint32_t *tiled, uint32_t width, uint32_t height, hipStream_t stream);
 hipError_t bc7_decode_launch(const uint8_t *blocks, uint8_t *rgba, uint32_t width, uint32_t height, hipStream_t stream);
 
+// ---- bcn.hip ------------------------------------------------------------------------------------------------------
+// A DDS chain of BC1-BC5 blocks or BGRA8 / BGRX8 texels -> RGBA8 (rules D1-D7 in bcn.hip), every level in ONE launch.  Level m of the
+// source starts where level m - 1 ends (ceil(w / 4) * ceil(h / 4) blocks of bcn_block_bytes(format), or w * h texels); level m of `rgba` at
+// mipOffset[m] texels.  BGRA8 / BGRX8 convert in place: pass src == rgba, holding the file's texels.
+enum BcnFormat : uint32_t { BCN_BC1 = 1, BCN_BC2, BCN_BC3, BCN_BC4, BCN_BC5, BCN_BGRA8, BCN_BGRX8 };
+uint32_t bcn_block_bytes(uint32_t format);           // 8 (BC1, BC4) or 16 (BC2, BC3, BC5)
+hipError_t bcn_decode_launch(const uint8_t *src, uint8_t *rgba, uint32_t format, const uint32_t *mipOffset, uint32_t width, uint32_t height, int levels, hipStream_t stream);
+
 // ---- mipgen.hip ---------------------------------------------------------------------------------------------------
 // Mip chain of an RGBA8 texture (device option generate_mipmaps; rules M1-M6 in mipgen.hip): level 0 is in place at mipOffset[0], the
 // launches make levels 1 .. levels - 1.  A chain whose level 1 holds at most MIPGEN_TAIL_TEXELS texels is one launch of one workgroup.

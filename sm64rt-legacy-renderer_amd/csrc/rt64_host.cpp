@@ -556,45 +556,100 @@ void Texture::setRGBA8(const void *bytes, int byteCount, int w, int h, int rowPi
 
 static uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
+// The DDS pixel formats RT64_CreateTexture accepts (the reference loader's mapping, DDSTextureLoader12.cpp:566-578, 722-769, 831-849) and how a
+// level is stored in the file: `blockDim` x `blockDim` texels in `blockBytes` bytes.  RGBA8 is copied as it is, BC7 goes to bc7.hip, the rest to
+// bcn.hip (rules D1-D7).  The _SRGB variants keep their stored bytes (D7).
+struct DdsFormat { const char *name; uint32_t bcn; uint32_t blockDim, blockBytes; bool bc7; };
+static const DdsFormat DDS_RGBA8 = { "R8G8B8A8_UNORM", 0, 1, 4, false }, DDS_BC7 = { "BC7_UNORM", 0, 4, 16, true },
+    DDS_BC1 = { "BC1_UNORM", BCN_BC1, 4, 8, false }, DDS_BC2 = { "BC2_UNORM", BCN_BC2, 4, 16, false }, DDS_BC3 = { "BC3_UNORM", BCN_BC3, 4, 16, false },
+    DDS_BC4 = { "BC4_UNORM", BCN_BC4, 4, 8, false }, DDS_BC5 = { "BC5_UNORM", BCN_BC5, 4, 16, false },
+    DDS_BGRA8 = { "B8G8R8A8_UNORM", BCN_BGRA8, 1, 4, false }, DDS_BGRX8 = { "B8G8R8X8_UNORM", BCN_BGRX8, 1, 4, false };
+static const char *const DDS_ACCEPTED = "accepted: BC1-BC5 UNORM (DXT1-DXT5, ATI1, ATI2, BC4U, BC5U), BC7, R8G8B8A8, B8G8R8A8, B8G8R8X8";
+
+static const DdsFormat &dds_dxgi_format(uint32_t fmt) {
+    switch (fmt) {
+    case 28: case 29: return DDS_RGBA8;
+    case 71: case 72: return DDS_BC1;
+    case 74: case 75: return DDS_BC2;
+    case 77: case 78: return DDS_BC3;
+    case 80: return DDS_BC4;
+    case 83: return DDS_BC5;
+    case 87: case 91: return DDS_BGRA8;
+    case 88: case 93: return DDS_BGRX8;
+    case 98: case 99: return DDS_BC7;
+    }
+    const char *why = (fmt == 81 || fmt == 84) ? "signed formats are not supported: the RGBA8 texel store holds no negative values"
+                    : (fmt >= 94 && fmt <= 96) ? "BC6H is an HDR format"
+                    : (fmt == 27 || fmt == 70 || fmt == 73 || fmt == 76 || fmt == 79 || fmt == 82 || fmt == 90 || fmt == 92 || fmt == 97) ? "typeless formats are not supported"
+                    : "unsupported";
+    throw std::runtime_error("RT64_CreateTexture: DXGI format " + std::to_string(fmt) + " in DDS: " + why + " (" + DDS_ACCEPTED + ").");
+}
+
+static const DdsFormat &dds_fourcc_format(uint32_t fourCC) {
+    char cc[5] = { (char)(fourCC & 0xFF), (char)((fourCC >> 8) & 0xFF), (char)((fourCC >> 16) & 0xFF), (char)(fourCC >> 24), 0 };
+    const std::string s(cc, 4);
+    if (s == "DXT1") return DDS_BC1;
+    if (s == "DXT2" || s == "DXT3") return DDS_BC2;              // DXT2 / DXT4: premultiplied alpha, decoded as stored (DDSTextureLoader12.cpp:737-743)
+    if (s == "DXT4" || s == "DXT5") return DDS_BC3;
+    if (s == "ATI1" || s == "BC4U") return DDS_BC4;
+    if (s == "ATI2" || s == "BC5U") return DDS_BC5;
+    for (char &ch : cc) if (ch && (ch < 0x20 || ch > 0x7E)) ch = '?';
+    const char *why = (s == "BC4S" || s == "BC5S") ? "signed formats are not supported: the RGBA8 texel store holds no negative values" : "unsupported";
+    throw std::runtime_error(std::string("RT64_CreateTexture: DDS FourCC '") + cc + "': " + why + " (" + DDS_ACCEPTED + ").");
+}
+
 void Texture::setDDS(const void *data, int byteCount) {
     const uint8_t *bytes = static_cast<const uint8_t *>(data);
     if (!bytes || byteCount < 128 || memcmp(bytes, "DDS ", 4) != 0) throw std::runtime_error("RT64_CreateTexture: not a DDS file.");
     uint32_t h = rd32(bytes + 12), w = rd32(bytes + 16), mipCount = rd32(bytes + 28);
     uint32_t pfFlags = rd32(bytes + 80), fourCC = rd32(bytes + 84), rgbBits = rd32(bytes + 88);
-    size_t off = 128; bool bc7 = false, rgba = false;
+    const uint32_t maskR = rd32(bytes + 92), maskG = rd32(bytes + 96), maskB = rd32(bytes + 100), maskA = rd32(bytes + 104);
+    size_t off = 128;
+    const DdsFormat *f = nullptr;
     if ((pfFlags & 0x4) && fourCC == 0x30315844u) {
         if (byteCount < 148) throw std::runtime_error("RT64_CreateTexture: truncated DX10 DDS header.");
-        uint32_t fmt = rd32(bytes + 128); off = 148;
-        if (fmt == 98 || fmt == 99) bc7 = true; else if (fmt == 28 || fmt == 29) rgba = true;
-        else throw std::runtime_error("RT64_CreateTexture: unsupported DXGI format in DDS (supported: BC7_UNORM, R8G8B8A8_UNORM).");
+        f = &dds_dxgi_format(rd32(bytes + 128)); off = 148;
     }
-    else if ((pfFlags & 0x40) && rgbBits == 32 && rd32(bytes + 92) == 0x000000FFu) rgba = true;
-    else throw std::runtime_error("RT64_CreateTexture: unsupported DDS pixel format.");
+    else if ((pfFlags & 0x40) && rgbBits == 32 && maskR == 0x000000FFu) f = &DDS_RGBA8;
+    else if ((pfFlags & 0x40) && rgbBits == 32 && maskR == 0x00FF0000u && maskG == 0x0000FF00u && maskB == 0x000000FFu && (maskA == 0xFF000000u || maskA == 0))
+        f = maskA ? &DDS_BGRA8 : &DDS_BGRX8;
+    else if (pfFlags & 0x4) f = &dds_fourcc_format(fourCC);
+    else throw std::runtime_error("RT64_CreateTexture: unsupported DDS pixel format (" + std::string(DDS_ACCEPTED) + ").");
     if (mipCount == 0) mipCount = 1;
     if (mipCount > RT64_MAX_MIPS || w == 0 || h == 0) throw std::runtime_error("RT64_CreateTexture: invalid DDS dimensions.");
+    // Level sizes in the file: ceil(w / blockDim) * ceil(h / blockDim) blocks of blockBytes each, the 1 x 1 and 2 x 2 levels included (D6).
+    size_t totalTexels = 0, totalSrc = 0, levelSrc[RT64_MAX_MIPS];
+    { uint32_t mw = w, mh = h;
+      for (uint32_t m = 0; m < mipCount; m++) {
+          mipOffset[m] = (uint32_t)totalTexels; totalTexels += (size_t)mw * mh;
+          levelSrc[m] = (size_t)((mw + f->blockDim - 1) / f->blockDim) * ((mh + f->blockDim - 1) / f->blockDim) * f->blockBytes; totalSrc += levelSrc[m];
+          mw = mw > 1 ? mw / 2 : 1; mh = mh > 1 ? mh / 2 : 1;
+      } }
+    if (off + totalSrc > (size_t)byteCount) throw std::runtime_error(std::string("RT64_CreateTexture: DDS data is truncated (") + f->name + ").");
     device->enter();
     width = (int)w; height = (int)h; mips = (int)mipCount;
-    size_t totalTexels = 0, totalSrc = 0;
-    { uint32_t mw = w, mh = h; for (uint32_t m = 0; m < mipCount; m++) { mipOffset[m] = (uint32_t)totalTexels; totalTexels += (size_t)mw * mh; totalSrc += bc7 ? (size_t)((mw + 3) / 4) * ((mh + 3) / 4) * 16 : (size_t)mw * mh * 4; mw = mw > 1 ? mw / 2 : 1; mh = mh > 1 ? mh / 2 : 1; } }
-    if (off + totalSrc > (size_t)byteCount) throw std::runtime_error("RT64_CreateTexture: DDS data is truncated.");
     texels.reserve(totalTexels * 4);
     uint8_t *stage = static_cast<uint8_t *>(device->staging(std::max(totalSrc, totalTexels * 4)));
     memcpy(stage, bytes + off, totalSrc);
-    if (bc7) {
-        DevArray<uint8_t> blocks; blocks.reserve(totalSrc);
-        HIP_CHECK(hipMemcpyAsync(blocks.ptr, stage, totalSrc, hipMemcpyHostToDevice, device->stream));
-        uint32_t mw = w, mh = h; size_t so = 0;
-        for (uint32_t m = 0; m < mipCount; m++) {
-            HIP_CHECK(bc7_decode_launch(blocks.ptr + so, texels.ptr + (size_t)mipOffset[m] * 4, mw, mh, device->stream));
-            so += (size_t)((mw + 3) / 4) * ((mh + 3) / 4) * 16; mw = mw > 1 ? mw / 2 : 1; mh = mh > 1 ? mh / 2 : 1;
-        }
+    if (f->blockDim == 1) {                   // 32-bit texels: straight into the texel store, BGRA8 / BGRX8 reordered in place
+        HIP_CHECK(hipMemcpyAsync(texels.ptr, stage, totalTexels * 4, hipMemcpyHostToDevice, device->stream));
+        if (f->bcn) HIP_CHECK(bcn_decode_launch(texels.ptr, texels.ptr, f->bcn, mipOffset, w, h, mips, device->stream));
         HIP_CHECK(hipStreamSynchronize(device->stream));
     }
     else {
-        HIP_CHECK(hipMemcpyAsync(texels.ptr, stage, totalTexels * 4, hipMemcpyHostToDevice, device->stream));
+        DevArray<uint8_t> blocks; blocks.reserve(totalSrc);
+        HIP_CHECK(hipMemcpyAsync(blocks.ptr, stage, totalSrc, hipMemcpyHostToDevice, device->stream));
+        if (f->bc7) {
+            uint32_t mw = w, mh = h; size_t so = 0;
+            for (uint32_t m = 0; m < mipCount; m++) {
+                HIP_CHECK(bc7_decode_launch(blocks.ptr + so, texels.ptr + (size_t)mipOffset[m] * 4, mw, mh, device->stream));
+                so += levelSrc[m]; mw = mw > 1 ? mw / 2 : 1; mh = mh > 1 ? mh / 2 : 1;
+            }
+        }
+        else HIP_CHECK(bcn_decode_launch(blocks.ptr, texels.ptr, f->bcn, mipOffset, w, h, mips, device->stream));      // the whole chain in one launch
         HIP_CHECK(hipStreamSynchronize(device->stream));
     }
-    // Alpha bounds for the opacity rule (read back once; texture creation is synchronous like the reference's).
+    // Alpha bounds for the opacity rule, over every level (read back once; texture creation is synchronous like the reference's).
     HIP_CHECK(hipMemcpy(stage, texels.ptr, totalTexels * 4, hipMemcpyDeviceToHost));
     uint8_t mn = 255, mx = 0;
     for (size_t i = 0; i < totalTexels; i++) { uint8_t a = stage[4 * i + 3]; mn = std::min(mn, a); mx = std::max(mx, a); }
