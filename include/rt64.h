@@ -398,7 +398,15 @@ enum {
     RT64_IMAGE_FIRST_INSTANCE_ID = 20, /* [i32]    copy used by GetViewRaytracedInstanceAt           */
     RT64_IMAGE_BACKGROUND = 21,        /* [u8 x 4] gBackground: raster background instances, screen size (zeros when there are none) */
     RT64_IMAGE_UPSCALED = 22,          /* [f32 x4] rtOutputUpscaled, screen size: colour + accumulated frames (only behind an upscaler) */
-    RT64_IMAGE_COUNT_ = 23
+    /* Debug images of the GI filter, render size like the images above; not views of visualization_mode.  They hold what the last frame that ran
+       the filter left: on a frame without GI or without the denoiser they are not written, and GI_MOMENTS / FILTER_GUIDE are not written by
+       denoiser_mode 0 either.  With primary_spp > 1 they describe the last sub-sample. */
+    RT64_IMAGE_GI_MOMENTS = 23,        /* [f32 x2] SVGF luminance moments (mu1, mu2) of the frame, as stored                  */
+    RT64_IMAGE_FILTER_GUIDE = 24,      /* [u32 x4] SVGF guide record, as the a-trous kernel reads it: normal x | y << 16 (f16 bits),
+                                                   normal z (f16 bits) | valid << 16, depth (f32 bits), depth gradient (f32 bits) */
+    RT64_IMAGE_FILTER_PING = 25,       /* [f32 x4] filter ping-pong image 0 (RGBA16F): after a frame, the input of the LAST pass (a-trous iteration 4,
+                                                   rgb + variance; or Gaussian pass 4, rgb + the raw image's history in alpha) */
+    RT64_IMAGE_COUNT_ = 26
 };
 
 /* Arrays returned by RT64_ReadbackMeshAccel / RT64_ReadbackViewAccel. */

@@ -121,6 +121,7 @@ def lib():
         "oracle_mesh_destroy": (None, [P]), "oracle_mesh_bvh": (C.POINTER(OBvh), [P]), "oracle_mesh_tris": (P, [P]),
         "oracle_render": (C.c_int, [P, C.POINTER(OFrameParams), C.POINTER(OFrameResult)]),
         "oracle_scene_tlas": (C.POINTER(OBvh), [P]), "oracle_scene_frame_count": (C.c_uint32, [P]),
+        "oracle_scene_filter_images": (None, [P, C.POINTER(_FP), C.POINTER(_FP)]),
         "oracle_init_rand": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
         "oracle_next_rand": (C.c_float, [C.POINTER(C.c_uint32)]),
         "oracle_halton": (C.c_float, [C.c_int, C.c_int]),
@@ -277,6 +278,9 @@ class OracleScene:
             "lockMask": img(r.lockMask, 1, np.float32), "depth": img(r.depth, 1, np.float32),
             "primaryHit": img(r.primaryHit, 4, np.uint32),
         }
+        mom, ping = _FP(), _FP()
+        self.L.oracle_scene_filter_images(self.scene, C.byref(mom), C.byref(ping))
+        out["moments"] = img(mom, 2, np.float32); out["filteredIndirectPing"] = img(ping, 4, np.float32)
         out["background"] = (np.ctypeslib.as_array(r.backgroundRGBA8, shape=(screen_h * screen_w * 4,)).copy().reshape(screen_h, screen_w, 4)
                              if r.backgroundRGBA8 else None)
         out["upscaled"] = (np.ctypeslib.as_array(r.upscaledRGBA32F, shape=(screen_h * screen_w * 4,)).copy().reshape(screen_h, screen_w, 4)

@@ -876,6 +876,11 @@ static void pass_post(OScene *s, const OFrameParams *p, const float *src, int sr
         }
 }
 
+void oracle_scene_filter_images(const OScene *s, const float **moments, const float **filteredIndirectPing) {
+    *moments = s->moments[s->rtSwap ^ 1];                /* (the end of a frame flips rtSwap: the last frame's set is the other one) */
+    *filteredIndirectPing = s->filteredIndirect[0];
+}
+
 int oracle_render(OScene *s, const OFrameParams *pIn, OFrameResult *out) {
     if (pIn->width <= 0 || pIn->height <= 0 || pIn->tileY0 < 0 || pIn->tileY1 > pIn->height || pIn->tileY0 >= pIn->tileY1) return 0;
     /* Screen size vs render size (View::createOutputBuffers, ref:rt64_view.cpp:138-139). */

@@ -194,6 +194,10 @@ const OTri *oracle_mesh_tris(const OMesh *m);
  * matrices, frameCount) lives in the scene, as in the reference's View. */
 int oracle_render(OScene *s, const OFrameParams *p, OFrameResult *out);
 const OBvh *oracle_scene_tlas(const OScene *s);
+/* GI filter images of the last rendered frame (render size, valid until the next render), kept out of OFrameResult so that its layout stays put:
+ * moments [h][w][2] = SVGF luminance moments (mu1, mu2); filteredIndirectPing [h][w][4] = filter ping-pong image 0, the input of the last a-trous /
+ * Gaussian pass. */
+void oracle_scene_filter_images(const OScene *s, const float **moments, const float **filteredIndirectPing);
 uint32_t oracle_scene_frame_count(const OScene *s);
 
 /* Small known-answer helpers exported for unit tests. */

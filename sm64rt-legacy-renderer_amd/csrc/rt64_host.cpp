@@ -1504,6 +1504,10 @@ static bool image_info(const ViewImages &I, int cur, int image, ImageInfo &info,
     case RT64_IMAGE_DEPTH: info = { I.depth[cur], 4, 1, 0 }; dstPixelBytes = 4; return true;
     case RT64_IMAGE_OUTPUT_RGBA32F: info = { I.output, 16, 4, 0 }; dstPixelBytes = 16; return true;
     case RT64_IMAGE_PRIMARY_HIT: info = { I.primaryHit, 16, 4, 0 }; dstPixelBytes = 16; return true;
+    // debug images of the GI filter (include/rt64.h): the moments and the guide records as stored, the a-trous / Gaussian ping-pong image 0
+    case RT64_IMAGE_GI_MOMENTS: info = { I.moments[cur], 8, 2, 0 }; dstPixelBytes = 8; return true;
+    case RT64_IMAGE_FILTER_GUIDE: info = { I.svgfGuide, 16, 4, 0 }; dstPixelBytes = 16; return true;
+    case RT64_IMAGE_FILTER_PING: info = { I.filteredIndirect[0], 8, 4, 1 }; dstPixelBytes = 16; return true;
     default: return false;
     }
 }

@@ -274,7 +274,10 @@ __global__ __launch_bounds__(256, 6) void svgf_atrous_kernel(const uint2 *__rest
                 const int ax = kx < 0 ? -kx : kx;
                 float e = 128.0f * fast_log2(fmaxf(0.0f, dot3(np[j], gq[kx + 2].n))) - (fabsf(zp[j] - gq[kx + 2].z) * kzd[ax] + fabsf(lp[j] - lq[kx + 2]) * kl[j]);
                 if (kx == 0) e = ky == 0 ? 0.0f : e;                                     // the centre tap carries the plain kernel weight
-                const float wt = (hx[kx + 2] * hy) * fast_exp2(fminf(e, 0.0f));
+                // e is NOT clamped at 0: with float16 normals n.n' may exceed 1 and max(0, n.n')^128 a little more than 1, as the spec and svgf_variance_kernel
+                // have it (a surface tap's e stays below 128 log2(1.002) < 0.4).  The bound of 1 only keeps the taps of weight 0 finite -- outside the frame or
+                // on sky, whose guide normal is no unit vector (n.n' reaches 3 and more): exp2(e) would overflow to +inf there, and 0 * inf is NaN
+                const float wt = (hx[kx + 2] * hy) * fast_exp2(fminf(e, 1.0f));
                 const f4 t = cq[kx + 2];
                 sw[j] += wt; sr[j] += wt * t.x; sg[j] += wt * t.y; sb[j] += wt * t.z; sv[j] += wt * wt * t.w;
             }
