@@ -53,7 +53,8 @@ hipError_t mipgen_launch(uint8_t *texels, const uint32_t *mipOffset, uint32_t wi
 // ---- passes.hip ---------------------------------------------------------------------------------------------------
 #define RT_CACHE_MAX_WORDS 1536       // LDS scene cache, nodes + instance records: at most 24 KB next to the 8 KB stack (int16 entries) and the light columns of a workgroup, four workgroups per CU
 #define RT_STACK_LDS 24               // traversal stack entries per lane in LDS of the kernels without the scene cache; deeper levels go to the HBM spill slab
-#define RT_STACK_LDS_CACHED 16        // traversal stack entries (LDS only, no spill path) of the kernels that hold the LDS scene cache: a power of two
+#define RT_STACK_LDS_CACHED 16        // traversal stack entries of the kernels that hold the LDS scene cache: the host enables the cache only when TLAS depth + the deepest
+                                      // BLAS fit in these entries (BlasHeader::depth), so their push / pop are plain LDS accesses -- no spill branch in the node loop; a power of two
 #define RT_STACK_SPILL 84             // entries per lane in the HBM slab behind the LDS entries
 #define RT_STACK_SPILL_HEADER 2       // uint32 words in front of EVERY lane's entries: the address of the overflow word (host-pinned memory); a lane's slab is RT_STACK_SPILL_HEADER + RT_STACK_SPILL words
 hipError_t launch_stack_slab_init(uint32_t *slab, size_t lanes, const uint32_t *flagDevicePointer, hipStream_t s);      // writes every lane's header
@@ -76,9 +77,9 @@ hipError_t launch_reflection(const FrameParams &P, const ViewImages &I, bool kli
 hipError_t launch_gaussian(const uint16_t *in, uint16_t *out, int width, int height, int y0, int y1, hipStream_t s);
 hipError_t launch_compose_post(const FrameParams &P, const ViewImages &I, int cur, bool lean, bool writeFinal, hipStream_t s);
 // A lean frame in one launch: primary visibility + resolve + direct light + compose (passes.hip, lean_frame_kernel).
+// Frames without the LDS scene cache run one wave (an 8 x 8 wave-tile) per workgroup, frames with it one 16 x 16 tile per workgroup.
 // maxGroups: cap of the grid (RT_MAX_FRAME_GROUPS; device option max_frame_groups lowers it so that small frames exercise the several-tiles-per-workgroup walk)
-// perWave: frames without the LDS scene cache run one wave (an 8 x 8 wave-tile) per workgroup instead of one 16 x 16 tile
-hipError_t launch_lean_frame(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, bool perWave, hipStream_t s);
+hipError_t launch_lean_frame(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, hipStream_t s);
 hipError_t launch_post_process(const FrameParams &P, const ViewImages &I, hipStream_t s);      // PostProcessPS as its own pass (resolution scale / motion blur)
 // DebugPS in PostProcess's place (device option visualization_mode): the image the view shows, as RT64_ReadbackDevice selects it -- its storage
 // (kind: 0 raw 32-bit words, 1 half floats, 2 unorm8; srcBytes per pixel) and, for modes 1, 2 and 5, the frame tag of the reflection passes' state
@@ -92,10 +93,10 @@ hipError_t launch_direct_simple(const FrameParams &P, const ViewImages &I, int c
 hipError_t launch_indirect_simple(const FrameParams &P, const ViewImages &I, int cur, bool writeFiltered, bool klist, int walk, unsigned groups, int writeGuide, hipStream_t s);
 hipError_t launch_refraction_simple(const FrameParams &P, const ViewImages &I, bool klist, hipStream_t s);
 hipError_t launch_reflection_simple(const FrameParams &P, const ViewImages &I, bool klist, int pass, bool last, int parity, hipStream_t s);
-hipError_t launch_lean_frame_simple(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, bool perWave, hipStream_t s);
+hipError_t launch_lean_frame_simple(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, hipStream_t s);
 hipError_t launch_clear_final(const FrameParams &P, const ViewImages &I, hipStream_t s);
 hipError_t launch_apply_reflection_state(const ViewImages &I, int width, int y0, int y1, uint32_t frameTag, hipStream_t s);      // rows [y0, y1): the continuation state the reflection passes tagged `frameTag` folded back into the G-buffer (readback only)
-unsigned lean_frame_tiles(const FrameParams &P);        // tiles of the one-kernel frame's launch (the device's rows, 16 x 16)
+unsigned owned_tiles(const FrameParams &P, bool rowTiles = false);     // 16 x 16 tiles (rowTiles: 32 x 8) of the rows this device owns: the host's count of what tile_count walks
 hipError_t launch_tile_order(uint32_t *cost, uint32_t *order, uint32_t tiles, hipStream_t s);
 hipError_t launch_spp_accumulate(const FrameParams &P, const ViewImages &I, float *sum, int sub, int count, hipStream_t s);
 

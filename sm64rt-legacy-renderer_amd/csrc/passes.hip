@@ -30,9 +30,6 @@
 #define RT_LAUNCHER(name) name
 #define RT_ROUTE_SIMPLE(call) if (P.simpleKernels) return call
 #endif
-#ifndef RT_ABLATE
-#define RT_ABLATE 0              // diagnostic builds (never shipped, tools/exp/r03_bounce_ablate.sh): parts of bounce_trace_plain_kernel stubbed out to price them
-#endif
 
 namespace {
 
@@ -43,10 +40,6 @@ struct Pixel { uint32_t x, y; bool valid; };
 //   ROWS   32x8,  wave = 32x2 pixels  : shading kernels (a wave's image store covers whole 128/256-byte lines)
 // Tile rows owned by this device: strips stripRank, stripRank + stripCount, ... of the 16-row strips in [tileY0, tileY1).
 enum TileShape { TILE_SQUARE = 0, TILE_ROWS = 1 };
-#ifndef RT_WAVE_BLOCK_W
-#define RT_WAVE_BLOCK_W 8        // pixels per row of a wave's block inside a SQUARE tile: 8 (8 x 8, shipped) or 16 (16 x 4: experiment of round 4, tools/exp/r04_wave_block.sh)
-#endif
-#define RT_WAVE_BLOCK_H (64 / RT_WAVE_BLOCK_W)
 template <int SHAPE> struct TileDim { static constexpr int W = SHAPE == TILE_SQUARE ? 16 : 32, H = SHAPE == TILE_SQUARE ? 16 : 8; };
 
 DEV uint32_t owned_strips(PRef P) {
@@ -62,13 +55,7 @@ template <int SHAPE = TILE_SQUARE> DEV Pixel tile_pixel_at(PRef P, uint32_t tile
     const uint32_t tx = tile % tilesX, lt = tile / tilesX;
     const uint32_t strip = (lt / perStrip) * (uint32_t)P.stripCount + (uint32_t)P.stripRank;
     Pixel p;
-    if (SHAPE == TILE_SQUARE) {
-#if RT_WAVE_BLOCK_W == 16
-        p.x = tx * TW + (lane & 15); p.y = wave * 4 + (lane >> 4);           // a wave owns 16 x 4 pixels: its stores are whole 64-byte pieces of image rows
-#else
-        p.x = tx * TW + (wave & 1) * 8 + (lane & 7); p.y = (wave >> 1) * 8 + (lane >> 3);
-#endif
-    }
+    if (SHAPE == TILE_SQUARE) { p.x = tx * TW + (wave & 1) * 8 + (lane & 7); p.y = (wave >> 1) * 8 + (lane >> 3); }
     else { p.x = tx * TW + (lane & 31); p.y = wave * 2 + (lane >> 5); }
     p.y += (uint32_t)P.tileY0 + strip * 16 + (lt % perStrip) * TH;
     p.valid = p.x < (uint32_t)P.width && p.y < (uint32_t)P.tileY1;
@@ -232,9 +219,7 @@ DEV bool surface_record(PRef P, IRef I, size_t pixel, uint32_t hit, const Surfac
     return surface_anyhit(P, b.y, a.w, __uint_as_float(b.x), __uint_as_float(a.y), __uint_as_float(a.z), dir, rayDiff, px, py, r);
 }
 
-#ifndef TRACE_WAVES
-#define TRACE_WAVES 4          // waves/SIMD the register allocator must fit for pure-traversal kernels (5 spills, measured no faster)
-#endif
+constexpr int TRACE_WAVES = 4;         // waves/SIMD the register allocator must fit for pure-traversal kernels (5 spills, measured no faster)
 // ---- primary visibility --------------------------------------------------------------------------------------------------
 
 template <bool KLIST, bool CACHED = false>
@@ -285,26 +270,12 @@ __global__ __launch_bounds__(RT_BLOCK, KLIST ? 2 : TRACE_WAVES) void primary_tra
 
 // TRANSPARENT_LIGHT: some instance is not provably opaque, so the 'transparent geometry that needs lighting' path of
 // PrimaryRayGen.hlsl:136-148 (one random light + shadow ray from inside the resolve loop) can be reached.
-#ifndef SHADE_TILE
-#define SHADE_TILE TILE_ROWS
-#endif
-#ifndef DIRECT_TILE
-#define DIRECT_TILE TILE_SQUARE
-#endif
-#ifndef SHADE_WAVES
-#define SHADE_WAVES 3
-#endif
-#ifndef DIRECT_WAVES
-#define DIRECT_WAVES 3
-#endif
+constexpr int SHADE_TILE = TILE_ROWS, DIRECT_TILE = TILE_SQUARE;
+constexpr int SHADE_WAVES = 3, DIRECT_WAVES = 3;
 // Without SLP pairs (csrc/Makefile) these two sit at 150 / 138 VGPRs: compiled for 4 waves per SIMD (128 VGPRs, 68 / 16 bytes of scratch per lane) they measure C5 2.89 -> 2.81 ms,
-// C3 / C4 unchanged (tools/exp/r04_waves_noslp.sh; the frame kernel at 4 waves: C2 0.154 -> 0.164, the two-phase bounce walk at 6: no change).
-#ifndef HIT_WAVES
-#define HIT_WAVES 4                   // bounce_hit_kernel walking from the LDS scene cache (the uncached form keeps DIRECT_WAVES: its 46 KB of LDS bound it to 3 anyway, and asked for 4 the compiler settles on 2)
-#endif
-#ifndef REFLECT_WAVES
-#define REFLECT_WAVES 4               // reflection_kernel walking from the LDS scene cache
-#endif
+// C3 / C4 unchanged (profiles/r04_experiments/compiler_flags.txt; the frame kernel at 4 waves: C2 0.154 -> 0.164, the two-phase bounce walk at 6: no change).
+constexpr int HIT_WAVES = 4;                  // bounce_hit_kernel walking from the LDS scene cache (the uncached form keeps DIRECT_WAVES: its 46 KB of LDS bound it to 3 anyway, and asked for 4 the compiler settles on 2)
+constexpr int REFLECT_WAVES = 4;              // reflection_kernel walking from the LDS scene cache
 // FULL = false ("lean" frame): no pass of this frame consumes the view direction, reflection / refraction / transparent
 // accumulators, motion vectors or upscaler masks, so they are not written (42 of 94 bytes per pixel); RT64_ReadbackDevice
 // re-runs the FULL variant on demand (View::materialise in rt64_host.cpp).
@@ -608,9 +579,7 @@ __global__ __launch_bounds__(RT_BLOCK, DIRECT_WAVES) void direct_kernel(FramePar
 // refraction, fog, motion blur downstream): it writes the reference's whole G-buffer like primary_shade_kernel<.., FULL> and
 // DirectRayGen's two images like direct_kernel<true>, and leaves Compose to its own pass.  ownedY0 / ownedY1: the rows DirectRayGen
 // covers (the frame parameters may include a denoiser halo above and below them, which only the G-buffer part renders).
-#ifndef LEAN_WAVES
-#define LEAN_WAVES 3          // waves per SIMD of the one-kernel frame: 3 (168 VGPRs) measured 12 % faster than 2 (193 VGPRs, no spills); 4 (128 VGPRs, 62 spilled dwords in the simple build) measured 30 % slower
-#endif
+constexpr int LEAN_WAVES = 3;          // waves per SIMD of the one-kernel frame: 3 (168 VGPRs) measured 12 % faster than 2 (193 VGPRs, no spills); 4 (128 VGPRs, 62 spilled dwords in the simple build) measured 30 % slower
 // BLOCK = 256: one 16 x 16 tile per workgroup trip, a wave owns an 8 x 8 quadrant (scenes with the LDS scene cache: its fill is shared by four waves).
 // BLOCK = 64 : the per-wave form for scenes that walk from HBM / L2 -- one 8 x 8 wave-tile per workgroup trip.  Nothing is shared between the waves of
 //              such a frame, and with one wave per workgroup every wave's registers AND its LDS are free the moment it ends: a tile whose four quadrants
@@ -714,9 +683,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void lean_frame_kernel(FrameParams Pv
             // in RGBA8 exactly as raster_draw_kernel would blend it over the stored pixel (rt64_view.cpp:1657-1661), without the launch
             uint32_t bits = (uint32_t)to_unorm8(result.x) | ((uint32_t)to_unorm8(result.y) << 8) | ((uint32_t)to_unorm8(result.z) << 16) | ((uint32_t)to_unorm8(1.0f) << 24);
             if (P.rasterFgCount) {
-                const int wx0 = __builtin_amdgcn_readfirstlane((int)(px & ~(uint32_t)(RT_WAVE_BLOCK_W - 1))), wy0 = __builtin_amdgcn_readfirstlane((int)(py & ~(uint32_t)(RT_WAVE_BLOCK_H - 1)));      // the wave's pixel block (8 x 8)
+                const int wx0 = __builtin_amdgcn_readfirstlane((int)(px & ~7u)), wy0 = __builtin_amdgcn_readfirstlane((int)(py & ~7u));      // the wave's pixel block (8 x 8)
                 bool loaded = true, dirty = false;
-                raster_blend_pixel(P.rasterFg, static_cast<const RasterTri *>(P.rasterFgTris), P.rasterFgCount, P.textures, (int)px, (int)py, true, wx0, wx0 + RT_WAVE_BLOCK_W - 1, wy0, wy0 + RT_WAVE_BLOCK_H - 1, nullptr, bits, loaded, dirty);
+                raster_blend_pixel(P.rasterFg, static_cast<const RasterTri *>(P.rasterFgTris), P.rasterFgCount, P.textures, (int)px, (int)py, true, wx0, wx0 + 7, wy0, wy0 + 7, nullptr, bits, loaded, dirty);
             }
             reinterpret_cast<uint32_t *>(I.final)[i] = bits;
             if (P.finalPacked) {        // the gather's send buffer: row r of the owned rows, strips back to back (same order as RT64_CopyDeviceImage)
@@ -733,13 +702,6 @@ __global__ __launch_bounds__(BLOCK, WAVES) void lean_frame_kernel(FrameParams Pv
         for (int d = 32; d >= 1; d >>= 1) { worst = max(worst, (uint32_t)__shfl_xor((int)worst, d, 64)); total += (uint32_t)__shfl_xor((int)total, d, 64); }
         if ((threadIdx.x & 63u) == 0u)
             P.tileTiming[2 * ((size_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)) + 1] = make_uint4((uint32_t)__builtin_amdgcn_s_memrealtime(), (uint32_t)__builtin_amdgcn_s_memtime(), worst, (total << 8) | 1u);
-#ifdef RT_PROFILE_TRIPS
-        uint32_t tn = env.cnt.tripsNode, tl = env.cnt.tripsLeaf, sm = env.cnt.spills, ss = env.cnt.spills;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { tn = max(tn, (uint32_t)__shfl_xor((int)tn, d, 64)); tl = max(tl, (uint32_t)__shfl_xor((int)tl, d, 64)); sm = max(sm, (uint32_t)__shfl_xor((int)sm, d, 64)); ss += (uint32_t)__shfl_xor((int)ss, d, 64); }
-        if ((threadIdx.x & 63u) == 0u)
-            P.tileTiming[(size_t)RT_TIMING_WAVES * 2 + (size_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)] = make_uint4(tn, tl, sm, ss);
-#endif
     }
     // counters: the primary rays' visits under PASS_PRIMARY_TRACE, the shadow rays' under PASS_DIRECT (same split as the separate kernels)
     TraceCounts directCnt = TraceCounts(); directCnt.nodes = env.cnt.nodes - primaryCnt.nodes; directCnt.tris = env.cnt.tris - primaryCnt.tris;
@@ -967,11 +929,7 @@ __global__ __launch_bounds__(RT_BLOCK, TRACE_WAVES) void bounce_trace_plain_kern
             const f3 rayDirection = cos_hemisphere_blue_noise(P, px, py, P.frameCount + smp * blueNoiseMult, shadingNormal);
             RayDiff rd; rd.dOdx = rd.dOdy = rd.dDdx = rd.dDdy = mk3s(0.0f);
             SurfaceHit best;
-#if RT_ABLATE >= 2
-            best.hit = false;                  // 2, 4: no walk
-#else
             trace_surface<false, CACHED>(P, env, I, i, rayOrigin, rayDirection, rd, px, py, best);
-#endif
             rays++;
             const size_t id = (size_t)(smp - 1) * stride + i;
             if (!best.hit) {
@@ -979,11 +937,7 @@ __global__ __launch_bounds__(RT_BLOCK, TRACE_WAVES) void bounce_trace_plain_kern
                 // list entry -- one 16-byte store instead of a 32-byte record, a list append, and a kernel that reads both back).  (Round 3 measured the
                 // third place for it: the direction and a mark in the result slot, the sky lookup in bounce_resolve_kernel.  C5: this kernel 1.334 -> 1.254 ms,
                 // the resolve 0.098 -> 0.266 ms -- worse; the lookup costs 0.08 ms here.)
-#if RT_ABLATE == 1 || RT_ABLATE == 2
-                const f3 resIndirect = ambientBase + rayDirection * (P.giSkyStrength * 1.0f);       // 1, 2: no sky lookup
-#else
                 const f3 resIndirect = ambientBase + bounce_sky_term(P, rayDirection) * (P.giSkyStrength * 1.0f);
-#endif
                 I.bounceResults[id] = BounceRadiance{ resIndirect.x, resIndirect.y, resIndirect.z };
                 continue;
             }
@@ -1016,7 +970,7 @@ __global__ __launch_bounds__(RT_BLOCK, TRACE_WAVES) void bounce_trace_plain_kern
 // Measured (MI355X, ms of the three bounce kernels, plain walk on a persistent grid of 2048 -> two phases, one workgroup per tile, 5 waves per SIMD): C5 (4 samples)
 // 1.81 -> 1.49, C4 (2 samples) 0.529 -> 0.487, C3 (1 sample) 0.233 -> 0.235: the host takes this form for frames with two or more samples per pixel.
 #define SPLIT_ITEMS 4u
-#define SPLIT_WAVES 5          // waves per SIMD (96 VGPRs, 13 dwords spilled outside the walk): 3 % faster than 4 on C4 / C5
+constexpr int SPLIT_WAVES = 5;         // waves per SIMD (96 VGPRs, 13 dwords spilled outside the walk): 3 % faster than 4 on C4 / C5
 template <bool CACHED>
 DEV bool tlas_reaches_a_leaf(PRef P, const f3 &o, const f3 &d, const TraceStack &stk, uint32_t &nodesVisited) {
     nodesVisited = 0;
@@ -1857,16 +1811,19 @@ size_t rt_stack_spill_bytes(int width, int rows) {
     blocks += 8;          // the per-wave frame rounds its grid up to whole groups of 8 tiles (32 one-wave workgroups)       // no launch has more workgroups than that (launch_lean_frame, sparse_grid)
     return blocks * RT_BLOCK * (RT_STACK_SPILL_HEADER + RT_STACK_SPILL) * sizeof(uint32_t);      // (a lane's entries + the header in front of them: trace.h)
 }
+// Host side of tile_count: the 16-row strips stripRank, stripRank + stripCount, ... of [tileY0, tileY1) are this device's.
+unsigned owned_tiles(const FrameParams &P, bool rowTiles) {
+    const unsigned all = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16;
+    const unsigned strips = all > (unsigned)P.stripRank ? (all - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
+    return rowTiles ? (unsigned)((P.width + 31) / 32) * strips * 2u : (unsigned)((P.width + 15) / 16) * strips;
+}
 #endif
 
 
 // Grid of a ray kernel: one persistent workgroup per CU slot (RT_GRID_BLOCKS), or one per tile when the device's share of the
 // frame has fewer tiles than that (small frames, a 1/8 strip share): workgroups without a tile only cost launch time.
 static unsigned rt_grid(const FrameParams &P) {
-    const unsigned all = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16;
-    const unsigned strips = all > (unsigned)P.stripRank ? (all - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
-    const unsigned tilesSquare = (unsigned)((P.width + 15) / 16) * strips, tilesRows = (unsigned)((P.width + 31) / 32) * strips * 2u;
-    const unsigned tiles = tilesSquare > tilesRows ? tilesSquare : tilesRows;
+    const unsigned tiles = owned_tiles(P, true);          // (never fewer than the 16 x 16 tiles: two 32 x 8 tiles per 32 columns of a strip)
     return tiles < 1u ? 1u : (tiles < (unsigned)RT_GRID_BLOCKS ? tiles : (unsigned)RT_GRID_BLOCKS);
 }
 #define LAUNCH_RAY(kernel, ...) do { hipLaunchKernelGGL(kernel, dim3(rt_grid(P)), dim3(RT_BLOCK), 0, s, __VA_ARGS__); return hipGetLastError(); } while (0)
@@ -1908,35 +1865,26 @@ hipError_t RT_LAUNCHER(launch_direct)(const FrameParams &P, const ViewImages &I,
 // CU), which together with the bottom-up tile order (geometry first) is a longest-job-first schedule; a resident round of
 // persistent workgroups with a static round-robin walk measured 8 % slower on the full frame (181 against 165 us) and keeps every
 // register file full until the launch ends, so nothing on another stream (the RCCL gather) can run beside it.
-#ifndef PERWAVE_WAVES
-#define PERWAVE_WAVES 3        // waves per SIMD of the per-wave (64-thread workgroup) form
-#endif
-hipError_t RT_LAUNCHER(launch_lean_frame)(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, bool perWave, hipStream_t s) {
-    RT_ROUTE_SIMPLE(launch_lean_frame_simple(P, I, hitInstance, cur, full, ownedY0, ownedY1, maxGroups, perWave, s));
-    const unsigned strips = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16, owned = strips > (unsigned)P.stripRank ? (strips - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
-    const unsigned tiles = (unsigned)((P.width + 15) / 16) * owned;
+hipError_t RT_LAUNCHER(launch_lean_frame)(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, int cur, bool full, int ownedY0, int ownedY1, unsigned maxGroups, hipStream_t s) {
+    RT_ROUTE_SIMPLE(launch_lean_frame_simple(P, I, hitInstance, cur, full, ownedY0, ownedY1, maxGroups, s));
+    const unsigned tiles = owned_tiles(P);
     // ... up to 8192 workgroups; bigger frames give every workgroup ceil(tiles / 8192) tiles (round-robin, same bottom-up order), which
     // amortises the scene-cache fill again (1440p: 2 tiles per workgroup, 4K: 4)
     if (maxGroups < 1u || maxGroups > RT_MAX_FRAME_GROUPS) maxGroups = RT_MAX_FRAME_GROUPS;
-    const size_t lds = cached_lds_bytes(P, true);       // the scene cache (when the frame has one) + the light-candidate columns of this frame's light count
     if (P.cacheWords) {
+        const size_t lds = cached_lds_bytes(P, true);       // the scene cache + the light-candidate columns of this frame's light count
         const unsigned perGroup = (tiles + maxGroups - 1u) / maxGroups, grid = tiles < 1u ? 1u : (tiles + perGroup - 1u) / perGroup;
         if (full) hipLaunchKernelGGL((lean_frame_kernel<true, true, LEAN_WAVES>), dim3(grid), dim3(RT_BLOCK), lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
         else hipLaunchKernelGGL((lean_frame_kernel<true, false, LEAN_WAVES>), dim3(grid), dim3(RT_BLOCK), lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
     }
-    else if (perWave) {
+    else {
         // one wave per workgroup: trips = 32 per 8 tiles (wave_tile_of), up to 4 x maxGroups workgroups, a multiple of 32 so that every trip of a workgroup stays on its XCD's tiles
         const unsigned trips = ((tiles + 7u) / 8u) * 32u, cap = maxGroups * 4u, perGroup = (trips + cap - 1u) / cap;
         unsigned grid = trips < 1u ? 32u : (trips + perGroup - 1u) / perGroup;
         grid = (grid + 31u) / 32u * 32u;
-        const size_t ldsWave = cached_lds_bytes(P, true) / (RT_BLOCK / 64) + 16;
-        if (full) hipLaunchKernelGGL((lean_frame_kernel<false, true, PERWAVE_WAVES, 64>), dim3(grid), dim3(64), ldsWave, s, P, I, hitInstance, cur, ownedY0, ownedY1);
-        else hipLaunchKernelGGL((lean_frame_kernel<false, false, PERWAVE_WAVES, 64>), dim3(grid), dim3(64), ldsWave, s, P, I, hitInstance, cur, ownedY0, ownedY1);
-    }
-    else {
-        const unsigned perGroup = (tiles + maxGroups - 1u) / maxGroups, grid = tiles < 1u ? 1u : (tiles + perGroup - 1u) / perGroup;
-        if (full) hipLaunchKernelGGL((lean_frame_kernel<false, true, LEAN_WAVES>), dim3(grid), dim3(RT_BLOCK), lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
-        else hipLaunchKernelGGL((lean_frame_kernel<false, false, LEAN_WAVES>), dim3(grid), dim3(RT_BLOCK), lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
+        const size_t ldsWave = cached_lds_bytes(P, true) / (RT_BLOCK / 64) + 16;      // the light-candidate columns of one wave
+        if (full) hipLaunchKernelGGL((lean_frame_kernel<false, true, LEAN_WAVES, 64>), dim3(grid), dim3(64), ldsWave, s, P, I, hitInstance, cur, ownedY0, ownedY1);
+        else hipLaunchKernelGGL((lean_frame_kernel<false, false, LEAN_WAVES, 64>), dim3(grid), dim3(64), ldsWave, s, P, I, hitInstance, cur, ownedY0, ownedY1);
     }
     return hipGetLastError();
 }
@@ -1950,8 +1898,7 @@ hipError_t RT_LAUNCHER(launch_indirect)(const FrameParams &P, const ViewImages &
     // grid of the bounce kernels: one workgroup per tile up to `groups` workgroups (0 = RT_MAX_BOUNCE_GROUPS), then tiles b, b + grid, ... (bounce_tile_of)
     unsigned grid = rt_grid(P);
     {
-        const unsigned all = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16, strips = all > (unsigned)P.stripRank ? (all - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
-        const unsigned tiles = (unsigned)((P.width + 15) / 16) * strips, most = P.cacheWords ? RT_MAX_BOUNCE_GROUPS : RT_MAX_FRAME_GROUPS /* the HBM spill slab of the traversal stacks is sized for that many workgroups */, cap = groups && groups < most ? groups : most;
+        const unsigned tiles = owned_tiles(P), most = P.cacheWords ? RT_MAX_BOUNCE_GROUPS : RT_MAX_FRAME_GROUPS /* the HBM spill slab of the traversal stacks is sized for that many workgroups */, cap = groups && groups < most ? groups : most;
         const unsigned per = tiles > cap ? (tiles + cap - 1) / cap : 1u;
         if (walk != BOUNCE_WALK_REFILL) grid = tiles < 1u ? 1u : (tiles + per - 1) / per;
     }
@@ -1981,9 +1928,7 @@ hipError_t launch_indirect_constant(const FrameParams &P, const ViewImages &I, i
 // Refraction / reflection only have work where the primary hit has the factor: most tiles return at once, so these two take one
 // workgroup per tile (up to 8192) and let the dispatcher balance them (C5 reflection: 0.315 -> 0.26 ms against the persistent grid).
 static unsigned sparse_grid(const FrameParams &P) {
-    const unsigned all = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16;
-    const unsigned strips = all > (unsigned)P.stripRank ? (all - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
-    const unsigned tiles = (unsigned)((P.width + 15) / 16) * strips;
+    const unsigned tiles = owned_tiles(P);
     return tiles < 1u ? 1u : (tiles < RT_MAX_FRAME_GROUPS ? tiles : RT_MAX_FRAME_GROUPS);
 }
 hipError_t RT_LAUNCHER(launch_refraction)(const FrameParams &P, const ViewImages &I, bool klist, hipStream_t s) {
@@ -2011,10 +1956,6 @@ hipError_t launch_compose_post(const FrameParams &P, const ViewImages &I, int cu
     if (lean) hipLaunchKernelGGL(compose_post_kernel<true>, grid, dim3(256), 0, s, P, I, cur, writeFinal ? 1 : 0);
     else hipLaunchKernelGGL(compose_post_kernel<false>, grid, dim3(256), 0, s, P, I, cur, writeFinal ? 1 : 0);
     return hipGetLastError();
-}
-unsigned lean_frame_tiles(const FrameParams &P) {
-    const unsigned strips = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16, owned = strips > (unsigned)P.stripRank ? (strips - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
-    return (unsigned)((P.width + 15) / 16) * owned;
 }
 hipError_t launch_tile_order(uint32_t *cost, uint32_t *order, uint32_t tiles, hipStream_t s) {
     hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, cost, order, tiles);

@@ -146,8 +146,6 @@ struct Options {
     bool hostTlas = true;         // the TLAS of up to RT64_HOST_TLAS_MAX instances is built on the host and travels in the table upload (0: always the GPU builder)
     bool simpleKernels = true;    // frames whose textures are all power-of-two sized and whose instances are all shadow-opaque run the kernels of passes_simple.hip
     bool ldsCache = true;         // small scenes: BVH nodes + instance records cached in LDS by the ray kernels (0: always walk from HBM/L2)
-    bool spinPresent = true;      // RT64_DrawDevice waits for the frame by polling the stream (0: blocking hipStreamSynchronize)
-    int perWaveFrame = -1;        // one-kernel frame of scenes without the LDS scene cache as one-wave workgroups (8 x 8 wave-tiles): 1 on, 0 off (16 x 16 tiles, four waves), -1 auto (on)
     bool tileTiming = false;      // profiling aid: the one-kernel frame records when each of its waves started and ended (RT64_ReadbackTileTiming)
     int bounceGroups = -1;        // cap of the bounce kernels' grid: 0 one workgroup per tile (up to RT_MAX_BOUNCE_GROUPS), n at most n workgroups (tiles b, b + n, ...), -1 auto (per tile for the two-phase walk, 1024 for the plain walk)
     int bounceSplit = -1;         // two-phase bounce walk (TLAS part first, survivors compacted through LDS): 1 on, 0 off, -1 auto (scenes with the LDS scene cache, two or more GI samples per pixel)
@@ -158,7 +156,6 @@ struct Options {
     bool foldVariance = true;      // ... and the filter's input (variance from the moments) for every pixel with four frames of history; svgf_variance_kernel then only runs where a younger pixel is marked (0: it makes every pixel's input)
     bool foldGuide = true;         // frames with the wavefront GI chain + SVGF: bounce_resolve_kernel writes the filter's guide records (0: svgf_guide_kernel, its own launch)
     bool overlapFrames = true;     // enqueued (sync_present = 0) pixel-local frames alternate over the render streams (three by default): frame k+1 starts while the last waves of frame k are still walking (Device::draw)
-    bool reflectionEarly = true;   // ... and they fork as soon as the G-buffer exists (beside the GI chain too), not only beside the a-trous iterations (0: round 3's placement)
     bool overlapReflection = true; // frames with reflection passes AND the SVGF denoiser: the reflection launches run on a second stream beside the a-trous iterations (they share no image)
     bool haloExchange = false;     // band partitions of GI + SVGF frames: ship the filter input of the halo rows between the devices of the gather (RCCL) instead of re-rendering them
     bool haloDryRun = false;       // timing aid: an exchanging band runs its frame but moves no halo rows (what one rank's GPU work costs, measured on one device; results outside the band's interior are then wrong)
@@ -1475,7 +1472,7 @@ void View::fillParams(FrameParams &P) {        // updateGlobalParamsBuffer, rt64
     }
     P.blueNoise = dev->blueNoise.ptr; P.counters = dev->counters.ptr;
     P.tileTiming = nullptr;
-    if (dev->opt.tileTiming) { dev->tileTiming.reserve((size_t)RT_TIMING_WAVES * 3); P.tileTiming = dev->tileTiming.ptr; }      // two records per wave + one more in diagnostic builds
+    if (dev->opt.tileTiming) { dev->tileTiming.reserve((size_t)RT_TIMING_WAVES * 2); P.tileTiming = dev->tileTiming.ptr; }      // two records per wave
 }
 
 struct ImageInfo { const void *ptr; int srcBytes; int channels; int kind; };   // kind: 0 raw copy, 1 half->float, 2 unorm8->float
@@ -1599,7 +1596,6 @@ void View::render() {                          // View::render, rt64_view.cpp:11
             X.tileY0 = std::max(0, P.tileY0 - halo); X.tileY1 = std::min(imgH, P.tileY1 + halo);
         }
         const bool lean = leanNow;
-        const bool perWave = dev->opt.perWaveFrame != 0;          // (only frames without the LDS scene cache take that form: launch_lean_frame)
         // A lean frame is pixel-local end to end: one kernel carries every pixel from the primary ray to the back buffer
         // (device option fused_lean = 0 keeps the three separate kernels; same back buffer bit for bit).
         const bool fused = lean && dev->opt.fusedLean;
@@ -1627,8 +1623,8 @@ void View::render() {                          // View::render, rt64_view.cpp:11
         // walks hundreds of dependent fetches): the launch is as long as its longest wave plus the time that wave waited to start.  Each tile's cost (the most visits any
         // of its lanes made) is recorded by the frame and the next frame starts its tiles most expensive first (tile_order_kernel; the scene changes little between frames).
         auto orderTiles = [&](FrameParams &F) -> unsigned {
-            if (!(dev->opt.tileOrder && perWave && !F.cacheWords)) return 0u;
-            const unsigned tiles = lean_frame_tiles(F);
+            if (!(dev->opt.tileOrder && !F.cacheWords)) return 0u;
+            const unsigned tiles = owned_tiles(F);
             if (tiles == 0u) return 0u;
             if (tileOrderTiles != tiles) {
                 dev->impure();
@@ -1657,12 +1653,12 @@ void View::render() {                          // View::render, rt64_view.cpp:11
         };
         // ... and from the moment the G-buffer exists when nothing else of the frame shares storage with them: their continuation state is their own (ViewImages::reflState0 / 1),
         // but the per-pixel hit lists of a k-buffer frame and the HBM half of the traversal stacks are per launch position, one set per frame -- such frames keep the later fork.
-        const bool reflectEarly = reflectBeside && !klist && !needSpillSlab && dev->opt.reflectionEarly;
+        const bool reflectEarly = reflectBeside && !klist && !needSpillSlab;
         if (fused) {
             // nullptr: the frame stores its back buffer only (hit records and the direct-light image come back through materialise); option lean_records = 1 keeps them
             if (P.tileTiming) { HIP_CHECK(hipMemsetAsync(dev->tileTiming.ptr, 0, dev->tileTiming.bytes(), s)); }
             const unsigned ordered = orderTiles(P);
-            L(launch_lean_frame(P, img, dev->opt.leanRecords ? hitInstance.ptr : nullptr, cur, false, 0, imgH, dev->opt.maxFrameGroups, perWave, s));
+            L(launch_lean_frame(P, img, dev->opt.leanRecords ? hitInstance.ptr : nullptr, cur, false, 0, imgH, dev->opt.maxFrameGroups, s));
             if (ordered) { L(launch_tile_order(tileCost[slot].ptr, tileOrder[slot].ptr, ordered, s)); tileOrderValid[slot] = true; }
             fusedStoreless = !dev->opt.leanRecords;
             mark(Device::EV_PRIMARY_TRACE); mark(Device::EV_PRIMARY); mark(Device::EV_DIRECT);
@@ -1671,7 +1667,7 @@ void View::render() {                          // View::render, rt64_view.cpp:11
             if (P.stripCount > 1 && (X.tileY0 != P.tileY0 || X.tileY1 != P.tileY1)) throw std::runtime_error("RT64_DrawDevice: interleaved strips with a denoiser halo.");
             if (X.tileTiming) { HIP_CHECK(hipMemsetAsync(dev->tileTiming.ptr, 0, dev->tileTiming.bytes(), s)); }
             const unsigned ordered = orderTiles(X);
-            L(launch_lean_frame(X, img, hitInstance.ptr, cur, true, P.tileY0, P.tileY1, dev->opt.maxFrameGroups, perWave, s));
+            L(launch_lean_frame(X, img, hitInstance.ptr, cur, true, P.tileY0, P.tileY1, dev->opt.maxFrameGroups, s));
             if (ordered) { L(launch_tile_order(tileCost[slot].ptr, tileOrder[slot].ptr, ordered, s)); tileOrderValid[slot] = true; }
             mark(Device::EV_PRIMARY_TRACE); mark(Device::EV_PRIMARY); mark(Device::EV_DIRECT);
             if (reflectEarly) reflectOnAux();              // beside the GI chain and the denoiser: joined before the composing iteration
@@ -1804,7 +1800,7 @@ void View::materialise() {
         Q.rasterFg = nullptr; Q.rasterFgTris = nullptr; Q.rasterFgCount = 0; Q.finalPacked = nullptr;
         Q.countTraversal = 0;        // the frame's rays were counted when the frame ran
         Q.tileTiming = nullptr;
-        HIP_CHECK(launch_lean_frame(Q, img, hitInstance.ptr, lastCur, true, Q.tileY0, Q.tileY1, dev->opt.maxFrameGroups, dev->opt.perWaveFrame != 0, dev->stream));
+        HIP_CHECK(launch_lean_frame(Q, img, hitInstance.ptr, lastCur, true, Q.tileY0, Q.tileY1, dev->opt.maxFrameGroups, dev->stream));
         HIP_CHECK(launch_indirect_constant(lastParams, img, lastCur, dev->stream));
     }
     else {
@@ -1877,13 +1873,10 @@ void Device::draw(int, float) {                // Device::draw, rt64_device.cpp:
     if (profNow) endEventSet();
     // postRender: Present + waitForGPU (:1006-1025).  Option sync_present = 0 turns RT64_DrawDevice into "enqueue the frame": the
     // host returns at once and orders its own work behind the frame on RT64_GetDeviceStream (pipelined multi-GPU gather in bench.py).
-    if (opt.syncPresent) {
-        if (opt.spinPresent) {       // poll instead of sleeping on the completion signal: the render thread is back ~10 us sooner
-            hipError_t q;
-            while ((q = hipStreamQuery(stream)) == hipErrorNotReady) { __builtin_ia32_pause(); }
-            HIP_CHECK(q);
-        }
-        else HIP_CHECK(hipStreamSynchronize(stream));
+    if (opt.syncPresent) {       // poll instead of sleeping on the completion signal: the render thread is back ~10 us sooner
+        hipError_t q;
+        while ((q = hipStreamQuery(stream)) == hipErrorNotReady) { __builtin_ia32_pause(); }
+        HIP_CHECK(q);
     }
     auto t1 = std::chrono::steady_clock::now();
     const unsigned dropped = traversalOverflow ? *traversalOverflow : 0u;       // (enqueued frames: whatever earlier frames have reported by now; RT64_GetDeviceStats waits for the last one)
@@ -2141,7 +2134,6 @@ RT64_EXPORT int RT64_SetDeviceOption(RT64_DEVICE *device, const char *key, doubl
     else if (k == "denoiser_mode") d->opt.denoiserMode = (int)value;
     else if (k == "bounce_refill") d->opt.bounceRefill = (int)value;
     else if (k == "overlap_reflection") d->opt.overlapReflection = value != 0.0;
-    else if (k == "reflection_early") d->opt.reflectionEarly = value != 0.0;
     else if (k == "overlap_frames") d->opt.overlapFrames = value != 0.0;       // 0: every frame on one render stream (a host that orders its own work behind frames on RT64_GetDeviceStream)
     else if (k == "tile_order") d->opt.tileOrder = value != 0.0;
     else if (k == "fold_variance") d->opt.foldVariance = value != 0.0;
@@ -2152,9 +2144,7 @@ RT64_EXPORT int RT64_SetDeviceOption(RT64_DEVICE *device, const char *key, doubl
     else if (k == "halo_margin") d->opt.haloMargin = std::max((int)value, SVGF_INPUT_HALO_ROWS);
     else if (k == "bounce_split") d->opt.bounceSplit = (int)value;
     else if (k == "bounce_groups") d->opt.bounceGroups = value >= 0.0 && value <= (double)RT_MAX_BOUNCE_GROUPS ? (int)value : -1;
-    else if (k == "per_wave_frame") d->opt.perWaveFrame = (int)value;
     else if (k == "tile_timing") d->opt.tileTiming = value != 0.0;
-    else if (k == "spin_present") d->opt.spinPresent = value != 0.0;
     else if (k == "lds_cache") d->opt.ldsCache = value != 0.0;
     else if (k == "lean_records") d->opt.leanRecords = value != 0.0;
     else if (k == "host_tlas") d->opt.hostTlas = value != 0.0;

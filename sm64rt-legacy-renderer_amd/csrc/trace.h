@@ -16,7 +16,7 @@
 // ds_write_b32/ds_read_b32; deeper entries spill to a per-resident-lane slab in HBM (never touched on the sample scene:
 // LBVH depth <= 30 + log2(n) per level).
 #pragma once
-#include "rt64_gpu.h"
+#include "kernels.h"          // RT_STACK_*: one definition for the kernels and the host that sizes their stacks
 #include "device_math.h"
 
 // Frame constants as the device functions see them: a reference into the constant address space (the kernel-argument segment),
@@ -38,17 +38,6 @@ DEV PPtr kernel_params_here() { uint32_t z; asm volatile("s_mov_b32 %0, 0" : "=s
 #define RT_BLOCK 256                 // threads per workgroup of the ray kernels (the per-wave form of the one-kernel frame runs 64)
 #define RT_LANES 64                  // lanes of a wave: the per-lane LDS columns (node stack, light candidates) are laid out [wave][entry][lane], so a
                                      // wave's push / pop is one conflict-free ds access and the layout does not depend on the workgroup size
-#ifndef RT_STACK_LDS
-#define RT_STACK_LDS 24                 // (kernels.h defines it for the host too)
-#endif
-#ifndef RT_STACK_SPILL
-#define RT_STACK_SPILL 84               // (kernels.h defines both for the host too) entries per lane in the HBM slab behind the LDS entries
-#define RT_STACK_SPILL_HEADER 2         // uint32 words in front of EVERY lane's entries: the address of the overflow word (host-pinned memory)
-#endif
-#ifndef RT_STACK_LDS_CACHED
-#define RT_STACK_LDS_CACHED 16           // (kernels.h defines it for the host too) kernels that also hold the LDS scene cache: the host enables the cache only when TLAS depth + the deepest BLAS fit in these
-                                        // entries (BlasHeader::depth), so their push / pop are plain LDS accesses -- no spill branch in the node loop
-#endif
 
 struct RaySpace { float o[3], d[3], inv[3], oi[3]; };
 
@@ -135,17 +124,7 @@ struct TraceStack {
     }
 };
 
-#ifdef RT_PROFILE_TRIPS       // diagnostic build (never shipped): how many trips of the node loop / leaf step a WAVE made, counted in SGPRs whatever the exec mask is
-struct TraceCounts { uint32_t nodes, tris, tripsNode, tripsLeaf, spills; };
-#define RT_TRIP_DECL(name) __shared__ uint32_t name##Lds[16]; if ((threadIdx.x & 63u) == 0u) name##Lds[threadIdx.x >> 6] = 0u; uint32_t name = 0
-#define RT_TRIP(name) do { if ((int)(threadIdx.x & 63u) == __ffsll((long long)__ballot(1)) - 1) name##Lds[threadIdx.x >> 6]++; } while (0)
-#define RT_TRIP_END(name) name = name##Lds[threadIdx.x >> 6]
-#else
 struct TraceCounts { uint32_t nodes, tris; };
-#define RT_TRIP_DECL(name)
-#define RT_TRIP(name)
-#define RT_TRIP_END(name)
-#endif
 
 // Pointers that were loaded from memory are "generic" to the compiler (flat_load + both wait counters).  Every BVH array
 // lives in HBM, so fetch through address space 1: global_load_dwordx4, vmcnt only.
@@ -217,7 +196,6 @@ DEV void trace_ray_stepwise(PRef P, const float o[3], const float d[3], float tm
     bool cull = false;
     uint32_t cur = 0;
     bool alive = true;
-    RT_TRIP_DECL(tripsNode); RT_TRIP_DECL(tripsLeaf);
     auto popNext = [&]() -> bool {
         if (blasBase >= 0 && sp == blasBase) { blasBase = -1; R = W; nodes = P.tlasNodes; }      // BLAS exhausted: resume the TLAS walk in world space
         if (sp == 0) return false;
@@ -225,7 +203,6 @@ DEV void trace_ray_stepwise(PRef P, const float o[3], const float d[3], float tm
         return true;
     };
     while (alive) {
-        RT_TRIP(tripsNode);
         const bool isNode = !(cur & RT64_LEAF_BIT), isTri = !isNode && cur != RT64_NO_CHILD && blasBase >= 0;
         NodeOrTri rec;
         if (isNode || isTri) {       // one fetch for both kinds of lane
@@ -272,21 +249,13 @@ DEV void trace_ray_stepwise(PRef P, const float o[3], const float d[3], float tm
         }
         else alive = popNext();
     }
-#ifdef RT_PROFILE_TRIPS
-    RT_TRIP_END(tripsNode); RT_TRIP_END(tripsLeaf);
-    cnt.tripsNode += tripsNode; cnt.tripsLeaf += tripsLeaf;
-#endif
 }
-
-#ifndef RT_STEPWISE_WALK
-#define RT_STEPWISE_WALK 1       // 0: scenes without the LDS scene cache keep the while-while loop too (A/B builds)
-#endif
 
 template <bool CACHED = false, class OnHit>
 DEV void trace_ray(PRef P, const float o[3], const float d[3], float tmin, float tmax, bool cullBackFaces,
                    const TraceStack &stk, OnHit &&onHit, TraceCounts &cnt) {
     if (P.instanceCount == 0) return;
-    if (!CACHED && RT_STEPWISE_WALK) { trace_ray_stepwise(P, o, d, tmin, tmax, cullBackFaces, stk, onHit, cnt); return; }
+    if (!CACHED) { trace_ray_stepwise(P, o, d, tmin, tmax, cullBackFaces, stk, onHit, cnt); return; }
     RaySpace W, R;
     make_ray_space(o, d, W);
     R = W;
@@ -301,22 +270,17 @@ DEV void trace_ray(PRef P, const float o[3], const float d[3], float tmin, float
     bool cull = false;
     uint32_t cur = 0;
     bool alive = true;
-    RT_TRIP_DECL(tripsNode); RT_TRIP_DECL(tripsLeaf);
     auto popNext = [&]() -> bool {
         if (blasBase >= 0 && sp == blasBase) {          // BLAS exhausted: resume the TLAS walk in world space
             blasBase = -1; R = W; nodes = P.tlasNodes; nodeOff = tlasOff;
         }
         if (sp == 0) return false;
-#ifdef RT_PROFILE_TRIPS
-        if (!CACHED && sp > stk.ldsEntries) cnt.spills++;
-#endif
         cur = stk.template pop<CACHED>(sp);
         return true;
     };
     while (alive) {
         // ---- inner nodes ----
         while (alive && !(cur & RT64_LEAF_BIT)) {
-            RT_TRIP(tripsNode);
             const GpuNode nd = CACHED ? load_node_lds(stk.cache + nodeOff + 4u * cur) : load_node(nodes + cur);
             cnt.nodes++;
             float tl, tr;
@@ -331,7 +295,6 @@ DEV void trace_ray(PRef P, const float o[3], const float d[3], float tmin, float
             else alive = popNext();
         }
         if (!alive) break;
-        RT_TRIP(tripsLeaf);
         // ---- leaf ----
         if (cur != RT64_NO_CHILD) {
             if (blasBase < 0) {
@@ -382,10 +345,6 @@ DEV void trace_ray(PRef P, const float o[3], const float d[3], float tmin, float
         }
         alive = popNext();
     }
-#ifdef RT_PROFILE_TRIPS
-    RT_TRIP_END(tripsNode); RT_TRIP_END(tripsLeaf);
-    cnt.tripsNode += tripsNode; cnt.tripsLeaf += tripsLeaf;
-#endif
 }
 
 // RayWalk: the same walk as trace_ray (same operations per ray, kept textually parallel) with its state in a struct so that it

@@ -29,18 +29,18 @@ for kv in a.option:
     k, _, v = kv.partition("="); assert s.option(k, float(v)), k
 if a.max_lights != 12:
     s.set_view_description(max_lights=a.max_lights)
-per_wave = not any(kv.replace(" ", "") == "per_wave_frame=0" for kv in a.option) and a.subdiv > 0
+per_wave = a.subdiv > 0          # scenes that walk from HBM (no LDS scene cache) run the frame as one-wave workgroups
 for _ in range(a.frames):
     s.draw()
 s.option("tile_timing", 1)
 s.draw(); s.draw()
 st = s.stats()
 NW = (8192 + 8) * 4
-rec = np.zeros((NW * 3, 4), dtype=np.uint32)
+rec = np.zeros((NW * 2, 4), dtype=np.uint32)
 n = lib.ReadbackTileTiming(s.device, rec.ctypes.data, rec.nbytes)
 assert n == rec.nbytes, lib.last_error()
 s.close()
-start, end, diag = rec[0:2 * NW:2], rec[1:2 * NW:2], rec[2 * NW:]
+start, end = rec[0::2], rec[1::2]
 ran = (start[:, 3] == 1) & ((end[:, 3] & 0xFF) == 1)
 t0 = start[ran, 0].astype(np.int64); t1 = end[ran, 0].astype(np.int64)
 cyc = (end[ran, 1].astype(np.int64) - start[ran, 1].astype(np.int64)) & 0xFFFFFFFF
@@ -84,12 +84,6 @@ print("the longest 1 %% of the waves: busiest lane %.0f visits on average (max %
     worst_lane[long_].mean(), worst_lane[long_].max(), total_visits[long_].mean() / 64.0, life[long_].sum() / max(worst_lane[long_].sum(), 1)))
 short_ = order[waves // 2:]
 print("the shorter half of the waves: busiest lane %.1f visits on average; %.3f us per visit of the busiest lane" % (worst_lane[short_].mean(), life[short_].sum() / max(worst_lane[short_].sum(), 1)))
-if diag[ran].any():          # diagnostic build (-DRT_PROFILE_TRIPS): wave-level trips of the node loop and of the leaf step, pops that went to the HBM spill slab
-    tn, tl, sm, ss = (diag[ran, k].astype(np.int64) for k in range(4))
-    print("DIAG all waves: node-loop trips %d, leaf trips %d, spill pops %d" % (tn.sum(), tl.sum(), ss.sum()))
-    for name, sel in (("longest 1 %", long_), ("shorter half", short_)):
-        print("DIAG %s: node trips %.0f, leaf trips %.0f per wave; busiest lane visits %.0f; spill pops per wave %.0f (worst lane %.0f); %.3f us per trip" % (
-            name, tn[sel].mean(), tl[sel].mean(), worst_lane[sel].mean(), ss[sel].mean(), sm[sel].mean(), life[sel].sum() / max((tn[sel] + tl[sel]).sum(), 1)))
 print("longest waves at pixel blocks (x, y): " + ", ".join("%s %.0f us / busiest lane %d visits" % (where(int(idx[j])), life[j], worst_lane[j]) for j in order[:12]))
 print("last waves to end: " + ", ".join("record %d (lived %.0f us, ended at %.0f us)" % (idx[j], life[j], (t1[j] - launch0) * 0.01) for j in last))
 if a.out:
