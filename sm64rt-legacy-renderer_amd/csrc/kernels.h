@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
+#include "../../include/rt64_query.h"
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -99,6 +100,12 @@ hipError_t launch_apply_reflection_state(const ViewImages &I, int width, int y0,
 unsigned owned_tiles(const FrameParams &P, bool rowTiles = false);     // 16 x 16 tiles (rowTiles: 32 x 8) of the rows this device owns: the host's count of what tile_count walks
 hipError_t launch_tile_order(uint32_t *cost, uint32_t *order, uint32_t tiles, hipStream_t s);
 hipError_t launch_spp_accumulate(const FrameParams &P, const ViewImages &I, float *sum, int sub, int count, hipStream_t s);
+
+// ---- query.hip -----------------------------------------------------------------------------------------------------
+// RT64_TraceViewRays: `count` RT64_RAYs -> RT64_RAY_HITs (device pointers, 16-byte aligned) against the tables of P (the view's last frame; rules Q1-Q7).
+// P.traversalStack: a slab of ray_query_spill_bytes() with its lane headers written, or nullptr when no walk of the scene outgrows the LDS stack.
+size_t ray_query_spill_bytes();
+hipError_t launch_ray_query(const FrameParams &P, const void *rays, void *hits, uint64_t count, uint32_t flags, hipStream_t s);
 
 // ---- raster.hip ----------------------------------------------------------------------------------------------------
 size_t raster_tri_bytes(uint32_t triTotal);       // setup records of a draw list

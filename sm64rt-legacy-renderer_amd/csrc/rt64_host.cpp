@@ -222,6 +222,11 @@ struct Device {
     uint32_t *traversalOverflow = nullptr;      // pinned host word the traversal stacks report a dropped entry to (TraceStack::report_overflow); read after every frame the host waits for
     void checkTraversalOverflow();
     DevArray<uint32_t> spillStack[RT64_RENDER_STREAMS_MAX];                                     // HBM half of the traversal stacks, one slab per render stream (indexed by the launch's lanes)
+    // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
+    // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
+    DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
+    DevArray<uint8_t> queryRays, queryHits;
+    void awaitQueries();          // host-waits for every query still enqueued on a caller stream (before a BLAS it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
     uint8_t *finalOverride = nullptr;     // direct gather (RT64_SetGatherDirect): the back buffer of the frame in hand IS the gather's frame slot -- on rank 0 its own memory, on the others rank 0's through an IPC mapping (peer stores over xGMI)
@@ -422,6 +427,7 @@ struct View {
         // only the BLAS node arrays behind it are copied by a kernel -- when a mesh of the frame was built, refitted or replaced, not when an instance moved
         const uint8_t *cacheImageAt = nullptr; std::vector<uint64_t> cacheBlasKey;
         unsigned readers = 0;                     // render streams (bit mask) whose frames have read the slot since its last upload
+        std::vector<hipEvent_t> queryEvents;      // ray queries enqueued on caller streams that read the slot: no frame uploads into it before they have completed
     } tab[TABLE_SLOTS];
     int tabCur = 0;
     std::vector<uint8_t> tableScratch;
@@ -434,6 +440,17 @@ struct View {
     bool fusedStoreless = false;              // ... and that kernel stored the back buffer only (no hit records, no direct-light image)
     bool fusedFrame = false;                  // ... and ran as lean_frame_kernel: rtOutput was not written either (unless PostProcess ran separately)
     FrameParams lastParams; int lastCur = 0;
+    // What ray queries (RT64_TraceViewRays, rules Q1-Q7) walk: the tables of the last frame, snapshot at the end of a successful RT64_DrawDevice
+    struct QueryScene {
+        bool valid = false;                       // a frame was drawn (a refused frame clears it: View::discardUpdate)
+        bool meshDestroyed = false;               // RT64_DestroyMesh on a mesh that frame traced
+        FrameParams P;                            // instances, TLAS, LDS scene-cache image of the frame's table slot
+        int slot = 0; bool needSpill = false;
+        std::vector<std::pair<Mesh *, uint32_t>> meshes;      // the meshes the frame traced and the version (RT64_SetMesh count) it traced
+        std::vector<Instance *> instances;                    // TLAS build position -> handle
+    } query;
+    void snapshotQueryScene();
+    void pruneQueryEvents(bool wait);             // forget the completed query events of every slot (wait: host-wait for the others first)
     // the last frame's reflection passes left their continuation state beside the G-buffer: a readback of the four images the reference rewrites folds it back first
     bool reflStatePending = false; uint32_t reflStateTag = 0; int reflStateY0 = 0, reflStateY1 = 0;
     void applyReflectionState();
@@ -486,6 +503,9 @@ Device::Device(int w, int h, int dev) {
     }
     HIP_CHECK(hipEventCreateWithFlags(&streamCatchUp, hipEventDisableTiming));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&traversalOverflow), 64, hipHostMallocMapped)); *traversalOverflow = 0;
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&queryOverflow), 64, hipHostMallocMapped)); *queryOverflow = 0;
+    HIP_CHECK(hipEventCreateWithFlags(&querySlabDone, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&queryOrder, hipEventDisableTiming));
     stream = streams[0]; cur = 0; seenEpoch[0] = orderedEpoch;
     for (auto &set : eventSets) for (auto &ev : set) HIP_CHECK(hipEventCreate(&ev));
     for (auto &set : auxEvents) for (auto &ev : set) HIP_CHECK(hipEventCreate(&ev));
@@ -508,6 +528,7 @@ Device::Device(int w, int h, int dev) {
 Device::~Device() {
     hipSetDevice(hipDevice);
     for (hipStream_t st : streams) if (st) hipStreamSynchronize(st);
+    try { awaitQueries(); } catch (...) {}
     if (getenv("RT64_HOST_TIMING") && hostFrames) fprintf(stderr, "RT64 host timing: %llu frames, View::update %.1f us, View::render %.1f us per frame\n", hostFrames, hostUpdateUs / (double)hostFrames, hostRenderUs / (double)hostFrames);
     if (getenv("RT64_HOST_TIMING") && hostFrames) { fprintf(stderr, "  launch host us by stage (up to each event mark):"); for (int i = 0; i < 16; i++) if (hostStageUs[i] > 0.0) fprintf(stderr, " [%d] %.1f", i, hostStageUs[i] / (double)hostFrames); fprintf(stderr, "  event records %.1f\n", hostEventUs / (double)hostFrames); }
     auto scenesCopy = scenes;
@@ -523,6 +544,10 @@ Device::~Device() {
     if (halo.done) hipEventDestroy(halo.done);
     if (ring) hipHostFree(ring);
     if (traversalOverflow) hipHostFree(traversalOverflow);
+    if (querySlabUsed) hipEventSynchronize(querySlabDone);
+    if (queryOverflow) hipHostFree(queryOverflow);
+    if (querySlabDone) hipEventDestroy(querySlabDone);
+    if (queryOrder) hipEventDestroy(queryOrder);
     for (hipEvent_t ev : streamJoin) if (ev) hipEventDestroy(ev);
     if (streamCatchUp) hipEventDestroy(streamCatchUp);
     for (hipStream_t st : streams) if (st) hipStreamDestroy(st);
@@ -724,6 +749,7 @@ void Mesh::set(const void *vertexArray, int vcount, int vstride, const unsigned 
     memcpy(hostBmin, mn, 12); memcpy(hostBmax, mx, 12);
     device->enter();
     if (vertices.ptr) device->beforeSceneMutation();       // a kept lean frame may still read this mesh's arrays (a first upload changes nothing a frame has seen)
+    if (vertices.ptr) device->awaitQueries();              // ... and so may a ray query on a caller stream (its BLAS is refitted in place or reallocated below)
     // rt64_mesh.cpp:30-39,76-82: a change of counts/stride discards the BLAS even if updatable.
     const bool sameShape = vertices.ptr && vertexCount == vcount && vertexStride == vstride && indexCount == icount;
     // A build that is still only recorded has to run on the arrays it was recorded for when this call is going to REFIT its tree (the
@@ -759,6 +785,14 @@ void Mesh::set(const void *vertexArray, int vcount, int vstride, const unsigned 
 
 Mesh::~Mesh() {
     if (buildPending) { auto &d = device->dirtyMeshes; d.erase(std::remove(d.begin(), d.end(), this), d.end()); }
+    // a view whose last frame traced this mesh answers no ray query until its next frame (Q7); one still enqueued on a caller stream finishes first
+    try { device->awaitQueries(); } catch (...) {}
+    for (Scene *sc : device->scenes) for (View *v : sc->views)
+        for (auto &m : v->query.meshes) if (m.first == this) { v->query.meshDestroyed = true; m.first = nullptr; }
+}
+
+void Device::awaitQueries() {
+    for (Scene *sc : scenes) for (View *v : sc->views) v->pruneQueryEvents(true);
 }
 
 // The recorded BLAS work of every mesh set since the last frame (the reference executes its upload command list the same way at the
@@ -861,6 +895,7 @@ View::View(Scene *s) : scene(s) {
     createImages(s->device->width, s->device->height, s->device->width, s->device->height);
 }
 View::~View() {
+    try { pruneQueryEvents(true); } catch (...) {}
     auto &v = scene->views; v.erase(std::remove(v.begin(), v.end(), this), v.end());
     releaseImages();
 }
@@ -1028,6 +1063,7 @@ void View::discardPrologue() {
 // A frame refused half-way through View::update: besides the unqueued work, the texture slots it handed out (Texture::currentIndex) are still set -- the
 // next frame would take them for its own and leave those textures out of its table.
 void View::discardUpdate() {
+    query.valid = false;                       // the refused frame may have moved the tables to another slot: no query until the next frame (Q7)
     for (Texture *t : usedTextures) t->currentIndex = -1;
     usedTextures.clear();
     discardPrologue();
@@ -1254,10 +1290,12 @@ void View::update() {                          // View::update, rt64_view.cpp:10
     // that waits for every frame alternates between two -- or, if there is none, the next one, behind a wait for the other streams.
     if (!unchanged) {
         int pick = -1;
-        for (int k = 1; k < TABLE_SLOTS && pick < 0; k++) { const int c = (tabCur + k) % TABLE_SLOTS; if (!(tab[c].readers & ~(1u << dev->cur))) pick = c; }
+        pruneQueryEvents(false);
+        for (int k = 1; k < TABLE_SLOTS && pick < 0; k++) { const int c = (tabCur + k) % TABLE_SLOTS; if (!(tab[c].readers & ~(1u << dev->cur)) && tab[c].queryEvents.empty()) pick = c; }
         if (pick < 0) { pick = (tabCur + 1) % TABLE_SLOTS; dev->impure(); }
         tabCur = pick;
         tab[tabCur].readers = 0;
+        for (hipEvent_t ev : tab[tabCur].queryEvents) HIP_CHECK(hipStreamWaitEvent(dev->stream, ev, 0));      // a ray query on a caller stream still reads the slot: the upload waits for it
         // TLAS: full rebuild (rt64_view.cpp:412-452 rebuilds every frame, updateOnly = false) -- of a few instances on the host, into the same upload
         const uint32_t n = (uint32_t)nInst;
         const bool hostTlas = n >= 1 && n <= RT64_HOST_TLAS_MAX && dev->opt.hostTlas;
@@ -1868,6 +1906,7 @@ void Device::draw(int, float) {                // Device::draw, rt64_device.cpp:
     }
     if (leanHoldoff) leanHoldoff--;
     lastFramePure = framePure;
+    for (Scene *sc : scenes) for (View *v : sc->views) v->snapshotQueryScene();
     auto tu2 = std::chrono::steady_clock::now();
     hostUpdateUs += std::chrono::duration<double, std::micro>(tu1 - tu0).count(); hostRenderUs += std::chrono::duration<double, std::micro>(tu2 - tu1).count(); hostFrames++;
     if (profNow) endEventSet();
@@ -2065,6 +2104,99 @@ static size_t readback(Device *dev, int image, void *dst, size_t dstBytes, bool 
     return need;
 }
 
+// ---- ray queries (RT64_TraceViewRays, include/rt64_query.h; rules Q1-Q7 in DESIGN.md 4) ---------------------------------------------------
+
+// The tables of the frame just drawn: what queries walk until the next frame.
+void View::snapshotQueryScene() {
+    query.valid = true; query.meshDestroyed = false; query.slot = tabCur; query.needSpill = needSpillSlab;
+    query.meshes.clear(); query.instances.clear();
+    for (const RenderInstance &ri : rtInstances) { query.meshes.emplace_back(ri.instance->mesh, ri.instance->mesh->version); query.instances.push_back(ri.instance); }
+    if (!rtInstances.empty()) query.P = lastParams;          // (View::render keeps the parameters of a frame with ray-traced instances)
+    else memset(&query.P, 0, sizeof(query.P));                // instanceCount 0: every ray misses
+}
+
+void View::pruneQueryEvents(bool wait) {
+    for (TableSlot &T : tab) {
+        std::vector<hipEvent_t> &E = T.queryEvents;
+        for (size_t k = 0; k < E.size();) {
+            if (wait) HIP_CHECK(hipEventSynchronize(E[k]));
+            const hipError_t q = wait ? hipSuccess : hipEventQuery(E[k]);
+            if (q == hipSuccess) { hipEventDestroy(E[k]); E[k] = E.back(); E.pop_back(); }
+            else if (q == hipErrorNotReady) k++;
+            else HIP_CHECK(q);
+        }
+    }
+}
+
+static void query_overflow_check(Device *dev, const char *fn) {
+    if (*dev->queryOverflow == 0u) return;
+    const unsigned n = *dev->queryOverflow; *dev->queryOverflow = 0;
+    throw std::runtime_error(std::string(fn) + ": " + std::to_string(n) + " traversal-stack entries were dropped by ray queries (TLAS depth + BLAS depth exceed " +
+                             std::to_string(RT_STACK_LDS + RT_STACK_SPILL) + " levels): their hits are missing geometry.");
+}
+
+// hostArrays: rays / hits in host memory, staged in chunks through pinned memory on the device's stream.  Otherwise device arrays, on `stream` (NULL: the device's stream).
+static void trace_view_rays(const char *fn, View *v, const void *rays, void *hits, size_t count, unsigned flags, void *stream, bool hostArrays) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    if (!v) fail("NULL view.");
+    if (!rays || !hits) fail("NULL ray or hit array.");
+    if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RAY_FLAG_ACCEPT_FIRST_HIT)) fail("unknown flags.");
+    if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u)) fail("the ray and hit arrays must be 16-byte aligned.");
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    // Q7: the BLASes the frame traced must still be the ones it traced
+    if (!q.valid) fail("the view has no frame to query (draw one first).");
+    if (q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
+    for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
+    dev->use();
+    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
+    if (count == 0) return;
+    dev->enter();                                // the device's stream is now behind every render stream: behind the last frame
+    v->pruneQueryEvents(false);
+    FrameParams P = q.P;
+    P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
+    P.tileTiming = nullptr; P.traversalStack = nullptr;
+    if (q.needSpill) {         // the walk can outgrow its LDS entries: the query's own slab, sized for its launch
+        const size_t words = ray_query_spill_bytes() / sizeof(uint32_t);
+        if (dev->querySlab.count < words) {
+            dev->querySlab.reserve(words);
+            void *flagDev = nullptr;
+            HIP_CHECK(hipHostGetDevicePointer(&flagDev, dev->queryOverflow, 0));
+            HIP_CHECK(launch_stack_slab_init(dev->querySlab.ptr, words / (RT_STACK_SPILL_HEADER + RT_STACK_SPILL), static_cast<const uint32_t *>(flagDev), dev->stream));
+        }
+        P.traversalStack = dev->querySlab.ptr;
+    }
+    const hipStream_t s = (!hostArrays && stream) ? static_cast<hipStream_t>(stream) : dev->stream;
+    if (s != dev->stream) { HIP_CHECK(hipEventRecord(dev->queryOrder, dev->stream)); HIP_CHECK(hipStreamWaitEvent(s, dev->queryOrder, 0)); }
+    if (P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slab
+    if (hostArrays) {
+        const size_t chunk = std::min<size_t>(count, (size_t)1 << 20), bytes = chunk * sizeof(RT64_RAY);
+        dev->queryRays.reserve(bytes); dev->queryHits.reserve(bytes);
+        uint8_t *pin = static_cast<uint8_t *>(dev->staging(bytes, 1));
+        for (size_t at = 0; at < count; at += chunk) {
+            const size_t n = std::min(chunk, count - at);
+            memcpy(pin, static_cast<const uint8_t *>(rays) + at * sizeof(RT64_RAY), n * sizeof(RT64_RAY));
+            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, pin, n * sizeof(RT64_RAY), hipMemcpyHostToDevice, s));
+            HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
+            HIP_CHECK(hipMemcpyAsync(pin, dev->queryHits.ptr, n * sizeof(RT64_RAY_HIT), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            memcpy(static_cast<uint8_t *>(hits) + at * sizeof(RT64_RAY_HIT), pin, n * sizeof(RT64_RAY_HIT));
+        }
+    }
+    else HIP_CHECK(launch_ray_query(P, rays, hits, count, flags, s));
+    if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
+    if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes) stay as they are until the query has run
+        hipEvent_t done = nullptr;
+        HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        const hipError_t e = hipEventRecord(done, s);
+        if (e != hipSuccess) { hipEventDestroy(done); HIP_CHECK(e); }
+        v->tab[q.slot].queryEvents.push_back(done);
+        return;
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    query_overflow_check(dev, fn);
+}
+
 }  // namespace rt64
 
 // ======================================================================================================================================
@@ -2213,6 +2345,18 @@ RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstanceAt(RT64_VIEW *viewPtr, i
     if (id >= 0 && (size_t)id < v->rtInstances.size()) return reinterpret_cast<RT64_INSTANCE *>(v->rtInstances[id].instance);
     return nullptr;
     RT64_CATCH(nullptr)
+}
+// ---- ray queries (include/rt64_query.h) ----
+RT64_EXPORT int RT64_TraceViewRays(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, size_t count, unsigned int flags) {
+    RT64_TRY trace_view_rays("RT64_TraceViewRays", reinterpret_cast<View *>(view), rays, hits, count, flags, nullptr, true); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRaysDevice(RT64_VIEW *view, const void *rays, void *hits, size_t count, unsigned int flags, void *stream) {
+    RT64_TRY trace_view_rays("RT64_TraceViewRaysDevice", reinterpret_cast<View *>(view), rays, hits, count, flags, stream, false); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {
+    const View *v = reinterpret_cast<View *>(viewPtr);
+    if (!v || !v->query.valid || instance < 0 || (size_t)instance >= v->query.instances.size()) return nullptr;
+    return reinterpret_cast<RT64_INSTANCE *>(v->query.instances[(size_t)instance]);
 }
 RT64_EXPORT bool RT64_GetViewUpscalerSupport(RT64_VIEW *viewPtr, int upscaler) {                       // rt64_view.cpp:2183 (declared (view, int) there)
     return viewPtr != nullptr && upscaler == RT64_UPSCALER_FSR;       // the built-in temporal upscaler answers for FSR; DLSS / XeSS: not initialised

@@ -220,6 +220,26 @@ EXT_API = [
     ("HaloPlan", "RT64_HaloPlan", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _P, C.c_int]),
     ("SetDeviceHaloExchange", "RT64_SetDeviceHaloExchange", C.c_int, [_P, _P, _P, C.POINTER(C.c_int), C.c_int, C.c_int]),
 ]
+# include/rt64_query.h: its own list and loader (RT64_LoadLibraryQuery), not part of exported_symbols() (the rt64.h list)
+QUERY_API = [
+    ("TraceViewRays", "RT64_TraceViewRays", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint]),
+    ("TraceViewRaysDevice", "RT64_TraceViewRaysDevice", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P]),
+    ("GetViewRaytracedInstance", "RT64_GetViewRaytracedInstance", _P, [_P, C.c_int]),
+]
+RAY_FLAG_CULL_BACK_FACING, RAY_FLAG_ACCEPT_FIRST_HIT = 0x1, 0x2
+
+
+class RAY(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("tMin", C.c_float), ("direction", C.c_float * 3), ("tMax", C.c_float)]
+
+
+class RAY_HIT(C.Structure):
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int), ("primitive", C.c_uint),
+                ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint), ("reserved", C.c_uint)]
+
+
+assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32
+
 HALO_ROWS = 62
 HALO_BYTES_PER_PIXEL = 24
 
@@ -243,7 +263,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -257,3 +277,31 @@ class Library:
 def exported_symbols():
     """Every symbol include/rt64.h declares (33 reference exports + extensions)."""
     return [s for _, s, _, _ in API + EXT_API]
+
+
+def trace_rays(lib, view, rays, flags=0, stream=None):
+    """RT64_TraceViewRays on an (N, 8) float32 array of RT64_RAYs: origin xyz, tMin, direction xyz, tMax.
+
+    A NumPy array takes the host path; a torch CUDA tensor the device path, enqueued on `stream` (a torch stream; default the tensor's
+    current stream) behind the view's last frame.  Returns (N, 8) float32 hits of the same kind -- t, u, v, then instance, primitive,
+    nodesVisited, trianglesTested, reserved as int32 / uint32 bits (read them through `.view(int32)`).  Raises with RT64_GetLastError on a refusal."""
+    if type(rays).__module__.split(".")[0] == "torch":
+        import torch
+        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_cuda:
+            raise ValueError("rays: an (N, 8) float32 CUDA tensor")
+        rays = rays.contiguous()
+        hits = torch.empty_like(rays)
+        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+        if s != torch.cuda.current_stream(rays.device):
+            rays.record_stream(s); hits.record_stream(s)      # (the allocator must not hand the memory out again before the query has run)
+        ok = lib.TraceViewRaysDevice(view, rays.data_ptr(), hits.data_ptr(), rays.shape[0], flags, s.cuda_stream)
+    else:
+        import numpy as np
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: an (N, 8) float32 array")
+        hits = np.empty_like(rays)
+        ok = lib.TraceViewRays(view, rays.ctypes.data, hits.ctypes.data, rays.shape[0], flags)
+    if not ok:
+        raise RuntimeError(lib.last_error())
+    return hits

@@ -460,3 +460,19 @@ class Rt64Scene:
             self.lib.DestroyShader(self.shader)
             self.lib.DestroyDevice(self.device)        # deletes scenes -> views + instances (rt64_device.cpp:97-100)
             self.device = None
+
+
+def camera_rays(data: SceneData, width: int, height: int, pixels) -> np.ndarray:
+    """Pixel-centre camera rays of the view in `data` for a width x height frame, as (N, 8) float32 RT64_RAYs (origin, tMin = 0, direction,
+    tMax = +inf) for RT64_TraceViewRays.  primary_ray (csrc/shade.h) evaluated in float64: the direction of a frame's primary ray up to
+    rounding, so pixels near a silhouette may pick the other side.  pixels: (N, 2) integer x, y (row 0 at the top)."""
+    fov, zn, zf = float(data.fov), float(data.near), float(data.far)
+    h = math.cos(0.5 * fov) / math.sin(0.5 * fov); w = h / (width / height); rng = zf / (zn - zf)
+    proj = np.zeros((4, 4)); proj[0, 0] = w; proj[1, 1] = h; proj[2, 2] = rng; proj[2, 3] = -1.0; proj[3, 2] = rng * zn      # XMMatrixPerspectiveFovRH
+    proj_i = np.linalg.inv(proj); view_i = np.linalg.inv(np.asarray(data.view, dtype=np.float64))
+    px = np.asarray(pixels, dtype=np.float64).reshape(-1, 2)
+    nx = (px[:, 0] + 0.5) / width * 2.0 - 1.0; ny = (px[:, 1] + 0.5) / height * 2.0 - 1.0
+    target = np.stack([nx, -ny, np.ones_like(nx), np.ones_like(nx)], axis=1) @ proj_i
+    r = np.zeros((len(px), 8), dtype=np.float32)
+    r[:, 0:3] = view_i[3, :3]; r[:, 4:7] = target[:, :3] @ view_i[:3, :3]; r[:, 7] = np.inf
+    return r
