@@ -51,7 +51,7 @@ hipError_t bcn_decode_launch(const uint8_t *src, uint8_t *rgba, uint32_t format,
 int mipgen_level_count(int width, int height);       // M2: min(floor(log2(max(w, h))) + 1, RT64_MAX_MIPS)
 hipError_t mipgen_launch(uint8_t *texels, const uint32_t *mipOffset, uint32_t width, uint32_t height, int levels, hipStream_t stream);
 
-// ---- passes.hip ---------------------------------------------------------------------------------------------------
+// ---- passes.hip (the ray kernels that also exist as `_simple` twins) + image_passes.hip (everything compiled once) ----
 #define RT_CACHE_MAX_WORDS 1536       // LDS scene cache, nodes + instance records: at most 24 KB next to the 8 KB stack (int16 entries) and the light columns of a workgroup, four workgroups per CU
 #define RT_STACK_LDS 24               // traversal stack entries per lane in LDS of the kernels without the scene cache; deeper levels go to the HBM spill slab
 #define RT_STACK_LDS_CACHED 16        // traversal stack entries of the kernels that hold the LDS scene cache: the host enables the cache only when TLAS depth + the deepest

@@ -1,28 +1,28 @@
-// passes.hip -- the per-frame ray passes of the render path as HIP kernels (wave64, persistent workgroups).
+// passes.hip -- the ray kernels of the frame that exist TWICE, general and "simple" (wave64, workgroups of 256 threads walking pixel tiles).
 //
-// MI355X-side replacement of the DispatchRays / Dispatch / Draw sequence of View::render
-// (/root/reference/src/rt64lib/private/rt64_view.cpp:1321-1650) and of the HLSL entry points it runs:
-//   primary_trace + primary_shade  <- PrimaryRayGen (shaders/PrimaryRayGen.hlsl:31-198) + surface any-hit
+// MI355X-side replacement of the DispatchRays sequence of View::render (the reference's src/rt64lib/private/rt64_view.cpp:1321-1650)
+// and of the HLSL entry points it runs:
+//   primary_shade                  <- PrimaryRayGen (shaders/PrimaryRayGen.hlsl:31-198) + surface any-hit, over primary_trace's hit records
 //   direct                         <- DirectRayGen (shaders/DirectRayGen.hlsl:14-65) + shadow any-hit
-//   indirect                       <- IndirectRayGen (shaders/IndirectRayGen.hlsl:31-137)
+//   lean_frame                     <- the three above in one kernel, for frames whose instances are all provably opaque
+//   indirect, bounce_*             <- IndirectRayGen (shaders/IndirectRayGen.hlsl:31-137), in one kernel or as a wavefront chain
 //   refraction / reflection        <- RefractionRayGen.hlsl:19-117 / ReflectionRayGen.hlsl:25-143
-//   gaussian                       <- GaussianFilterRGB3x3CS.hlsl:21-82
-//   compose_post                   <- ComposePS.hlsl:18-37 + PostProcessPS.hlsl:13-36 (fused: one read of the G-buffer)
-// Differences in structure (not in results): primary visibility is a pure traversal kernel that writes a 16-byte hit
-// record per pixel, and shading runs as a second, traversal-free kernel over coherent hit records; images keep the
-// reference's storage formats so every quantisation point is preserved.
+// Everything that is compiled once -- primary visibility (a pure traversal kernel that writes a 16-byte hit record per pixel), the
+// image-space passes, the scene cache image -- is in image_passes.hip; pass_common.h holds what both files use (tiles, the kernel
+// prologue, the surface ray, launch shapes).  Images keep the reference's storage formats so every quantisation point is preserved.
 //
 // Launch shape: RT_GRID_BLOCKS persistent workgroups of 256 threads walk 16x16-pixel tiles round-robin; a wave owns an
 // 8x8 pixel block (coherent rays, coalesced 8-row image stores).  Consecutive workgroup ids land on different XCDs, so
 // neighbouring tiles spread over all eight L2s while each tile's BVH nodes stay hot in its own.
-#include "kernels.h"
-#include "shade.h"
+#include "pass_common.h"
 #include "raster_pixel.h"
 
-// This file is compiled twice.  passes_simple.hip defines RT_ASSUME_SIMPLE and includes it: the same ray kernels for frames whose
+// Every line of this file is compiled twice.  passes_simple.hip defines RT_ASSUME_SIMPLE and includes it: the same kernels for frames whose
 // textures all have power-of-two sizes and whose instances are all shadow-opaque (rule O2) -- the non-power-of-two addressing and the
-// shadow any-hit program are not compiled in, which takes a third of the instructions and most of the register spills out of the
-// shading kernels (the sample scene is such a frame).  FrameParams::simpleKernels routes a launch to the `_simple` twin.
+// shadow any-hit program (the two places in shade.h that read the macro) are not compiled in, which takes a third of the instructions and
+// most of the register spills out of the shading kernels (the sample scene is such a frame).  FrameParams::simpleKernels routes a launch
+// to the `_simple` twin.  Two kernels here come out the same in both builds, bounce_trace_refill_kernel and bounce_resolve_kernel (neither
+// samples a texture nor casts a shadow ray; tools/kernel_isa_diff.py --twins): they stay because launch_indirect starts them between twins.
 #ifdef RT_ASSUME_SIMPLE
 #define RT_LAUNCHER(name) name##_simple
 #define RT_ROUTE_SIMPLE(call)
@@ -33,237 +33,30 @@
 
 namespace {
 
-struct Pixel { uint32_t x, y; bool valid; };
-
-// Pixel tiles.  A workgroup (4 waves) owns one tile per loop trip; two shapes:
-//   SQUARE 16x16, wave = 8x8 pixels   : traversal kernels (coherent rays share BVH nodes)
-//   ROWS   32x8,  wave = 32x2 pixels  : shading kernels (a wave's image store covers whole 128/256-byte lines)
-// Tile rows owned by this device: strips stripRank, stripRank + stripCount, ... of the 16-row strips in [tileY0, tileY1).
-enum TileShape { TILE_SQUARE = 0, TILE_ROWS = 1 };
-template <int SHAPE> struct TileDim { static constexpr int W = SHAPE == TILE_SQUARE ? 16 : 32, H = SHAPE == TILE_SQUARE ? 16 : 8; };
-
-DEV uint32_t owned_strips(PRef P) {
-    const uint32_t all = (uint32_t)(P.tileY1 - P.tileY0 + 15) / 16;
-    return all > (uint32_t)P.stripRank ? (all - (uint32_t)P.stripRank + (uint32_t)P.stripCount - 1) / (uint32_t)P.stripCount : 0u;
-}
-template <int SHAPE = TILE_SQUARE> DEV uint32_t tile_count(PRef P) {
-    return (uint32_t)((P.width + TileDim<SHAPE>::W - 1) / TileDim<SHAPE>::W) * owned_strips(P) * (16u / TileDim<SHAPE>::H);
-}
-template <int SHAPE = TILE_SQUARE> DEV Pixel tile_pixel_at(PRef P, uint32_t tile, uint32_t wave, uint32_t lane) {
-    constexpr uint32_t TW = TileDim<SHAPE>::W, TH = TileDim<SHAPE>::H, perStrip = 16u / TH;
-    const uint32_t tilesX = ((uint32_t)P.width + TW - 1) / TW;
-    const uint32_t tx = tile % tilesX, lt = tile / tilesX;
-    const uint32_t strip = (lt / perStrip) * (uint32_t)P.stripCount + (uint32_t)P.stripRank;
-    Pixel p;
-    if (SHAPE == TILE_SQUARE) { p.x = tx * TW + (wave & 1) * 8 + (lane & 7); p.y = (wave >> 1) * 8 + (lane >> 3); }
-    else { p.x = tx * TW + (lane & 31); p.y = wave * 2 + (lane >> 5); }
-    p.y += (uint32_t)P.tileY0 + strip * 16 + (lt % perStrip) * TH;
-    p.valid = p.x < (uint32_t)P.width && p.y < (uint32_t)P.tileY1;
-    return p;
-}
-template <int SHAPE = TILE_SQUARE> DEV Pixel tile_pixel(PRef P, uint32_t tile) {
-    return tile_pixel_at<SHAPE>(P, tile, threadIdx.x >> 6, threadIdx.x & 63);
-}
-
-DEV bool row_owned(PRef P, int y) { return (((y - P.tileY0) / 16) % P.stripCount) == P.stripRank; }
-
-// wordsPerLane: uint32 words of the stack array per lane (RT_STACK_LDS, or RT_STACK_LDS_CACHED / 2 for the int16 stacks of the cached kernels)
-DEV TraceStack make_stack(PRef P, uint32_t *ldsStack, uint32_t wordsPerLane = RT_STACK_LDS) {
-    TraceStack s;
-    uint32_t *block = ldsStack + (threadIdx.x >> 6) * wordsPerLane * RT_LANES;       // this wave's [entry][lane] block
-    s.lds = (LdsU32Ptr)(block + (threadIdx.x & 63u));
-    s.lds16 = (LdsI16Ptr)block + (threadIdx.x & 63u);
-    s.spill = (GlobalU32Ptr)(P.traversalStack + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * (RT_STACK_SPILL_HEADER + RT_STACK_SPILL) + RT_STACK_SPILL_HEADER);
-    s.cache = nullptr; s.ldsEntries = RT_STACK_LDS;
-    return s;
-}
-// this lane's columns of the light-candidate arrays, [wave][slots][lane] (floats, then bytes)
-DEV void light_columns(ShadeEnv &env, float *intensities, uint8_t *indices, uint32_t slots) {
-    const uint32_t at = (threadIdx.x >> 6) * slots * RT_LANES + (threadIdx.x & 63u);
-    env.lightIntensity = intensities + at; env.lightIndex = indices + at;
-}
-
-// LDS scene cache, filled once per workgroup (all threads call it; ends with a barrier).  Layout in 16-byte words:
-//   [0, 4m)            one 64-byte record per TLAS leaf slot: (M[c], M[4+c], M[8+c], M[12+c]) for c = 0..2 of worldToObject, then
-//                      (instance | flags << 8 | word offset of its BLAS nodes << 16, depth bias, tris pointer lo, hi)
-//   [4m, 4m + 4 nT)    TLAS nodes, nT = max(m - 1, 1)
-//   [cacheNodeOffset)  the BLAS nodes of every instance (offsets assigned by View::update)
-// The host enables it (FrameParams::cacheWords != 0) when all of that is at most RT_CACHE_MAX_WORDS: small scenes, like the sample.
-// The image is assembled once per table change in HBM (scene_cache_image_kernel: the pointer chase tlasIndex -> instance -> node array
-// happens there, three dependent round trips); a workgroup's fill is then one flat copy whose loads are all in flight together.
-#ifndef RT_ASSUME_SIMPLE
-DEV uint32_t cache_child_ref(uint32_t c) { return (c & RT64_LEAF_BIT) ? (c == RT64_NO_CHILD ? c : (0xFFFF8000u | (c & RT_CACHE_INDEX_MASK))) : c; }
-DEV void copy_cache_nodes(const GpuNode *nodes, uint32_t count, u32x4 *dst) {      // word 3 of a node = (left, right, parent, pad): the child references become 16-bit
-    typedef const u32x4 __attribute__((address_space(1))) *G4;
-    G4 src = reinterpret_cast<G4>(reinterpret_cast<uintptr_t>(nodes));
-    for (uint32_t t = threadIdx.x; t < 4u * count; t += blockDim.x) {
-        u32x4 w = src[t];
-        if ((t & 3u) == 3u) { w.x = cache_child_ref(w.x); w.y = cache_child_ref(w.y); }
-        dst[t] = w;
-    }
-}
-// blasOnly: the head (instance records + TLAS nodes) arrived with the table upload, written by the host (View::update: hostCache); only the BLAS node arrays are copied
-__global__ __launch_bounds__(RT_BLOCK) void scene_cache_image_kernel(const GpuInstance *instances, const uint32_t *tlasIndex, const GpuNode *tlasNodes, uint32_t m, u32x4 *cache, int blasOnly) {
-    typedef u32x4 W4;
-    const uint32_t T = blockDim.x, tid = threadIdx.x;
-
-    for (uint32_t k = tid; k < m && !blasOnly; k += T) {
-        const uint32_t inst = tlasIndex[k];
-        const GpuInstance &in = instances[inst];
-        const float *M = in.worldToObject;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            W4 w; w.x = __float_as_uint(M[c]); w.y = __float_as_uint(M[4 + c]); w.z = __float_as_uint(M[8 + c]); w.w = __float_as_uint(M[12 + c]);
-            cache[4 * k + c] = w;
-        }
-        const uint64_t tp = reinterpret_cast<uint64_t>(in.tris);
-        W4 info; info.x = inst | ((in.flags & 0xFFu) << 8) | (in.cacheNodeOffset << 16); info.y = __float_as_uint(in.material.depthBias); info.z = (uint32_t)tp; info.w = (uint32_t)(tp >> 32);
-        cache[4 * k + 3] = info;
-    }
-    if (!blasOnly) copy_cache_nodes(tlasNodes, m > 1 ? m - 1 : 1u, cache + 4 * m);
-    for (uint32_t k = 0; k < m; k++) {                       // uniform: every thread walks the same instance list
-        const GpuInstance &in = instances[tlasIndex[k]];
-        copy_cache_nodes(in.nodes, in.triCount > 1 ? in.triCount - 1 : 1u, cache + in.cacheNodeOffset);
-    }
-}
-#endif
-DEV void fill_scene_cache(PRef P, u32x4_lds *cache) {
-    typedef const u32x4 __attribute__((address_space(1))) *G4;
-    G4 src = reinterpret_cast<G4>(reinterpret_cast<uintptr_t>(P.cacheImage));
-    const uint32_t words = P.cacheWords;
-    for (uint32_t t = threadIdx.x; t < words; t += RT_BLOCK) cache[t] = src[t];
-    __syncthreads();
-}
-
-DEV void flush_env(PRef P, const ShadeEnv &env, int pass, int rayCounter, uint32_t rays) {
-    flush_counts(P, env.cnt, pass);
-    if (!P.countTraversal) return;
-    unsigned long long a = rays, b = env.shadowRays;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_down(a, d, 64); b += __shfl_down(b, d, 64); }
-    if ((threadIdx.x & 63) == 0) { unsigned long long *ctr = P.counters + (size_t)(blockIdx.x % RT_COUNTER_STRIPES) * CTR_COUNT; if (a) atomicAdd(&ctr[rayCounter], a); if (b) atomicAdd(&ctr[CTR_SHADOW], b); }
-}
-
-// ---- surface rays ---------------------------------------------------------------------------------------------------------
-// Sort key = t - depthBias (WithDistanceBias, Instances.hlsli:17-19); ties keep the first-come hit like the reference's
-// strict '<' insertion (rt64_shader.cpp:557).  Hits on instances flagged opaque (rule O1) shorten tmax (R5):
-// lim = (t - depthBias) + maxDepthBias.
-//   KLIST = false: every instance of the frame is provably opaque -> the list degenerates to the closest hit (registers).
-//   KLIST = true : sorted insertion into the per-pixel list in HBM, 16 entries + 1 scratch slot, exactly the any-hit of
-//                  rt64_shader.cpp:547-581 (a hit that lands in slot 15 commits tmax; nhits keeps counting).
-struct SurfaceHit { float key, t, u, v; uint32_t instance, prim; bool hit; };
-
-template <bool KLIST, bool CACHED = false>
-DEV uint32_t trace_surface(PRef P, ShadeEnv &env, IRef I, size_t pixel, f3 o, f3 d, const RayDiff &rayDiff,
-                           uint32_t px, uint32_t py, SurfaceHit &best) {
-    float oo[3] = { o.x, o.y, o.z }, dd[3] = { d.x, d.y, d.z };
-    best.hit = false; best.key = INFINITY;
-    uint32_t nhits = 0;
+// Slot `hit` (at most RT64_MAX_HIT_QUERIES: 17 slots are allocated) of the pixel's sorted hit list (k-buffer): a = (key, u, v, primitive), b = (t, instance).
+// Reads beyond the allocated slots return an empty record like an out-of-bounds typed UAV load: the two readers below test for that before they fetch.
+DEV void klist_slot(PRef P, IRef I, size_t pixel, uint32_t hit, uint4 &a, uint2 &b) {
     const size_t stride = (size_t)P.width * (size_t)P.height;
-    trace_ray<CACHED>(P, oo, dd, RT_RAY_MIN_DISTANCE, RT_RAY_MAX_DISTANCE, true, env.stk,
-              [&](float t, float u, float v, uint32_t instance, uint32_t prim, float &tmax, uint32_t instFlags, float instDepthBias) -> bool {
-                  const GpuInstance &in = P.instances[instance];
-                  const float key = t - instDepthBias;
-                  if (!KLIST) {
-                      if (key < best.key) { best.key = key; best.t = t; best.u = u; best.v = v; best.instance = instance; best.prim = prim; best.hit = true; }
-                  }
-                  else {
-                      if (in.cc.optTextureEdge) {            // IgnoreHit() before the hit is stored (rt64_shader.cpp:502-511)
-                          HitRecord tmp;
-                          if (!surface_anyhit(P, instance, prim, t, u, v, d, rayDiff, px, py, tmp)) return false;
-                      }
-                      uint32_t hi = nhits < RT64_MAX_HIT_QUERIES ? nhits : RT64_MAX_HIT_QUERIES;
-                      while (hi > 0) {
-                          const uint4 prev = I.klistA[(size_t)(hi - 1) * stride + pixel];
-                          if (!(key < __uint_as_float(prev.x))) break;
-                          I.klistA[(size_t)hi * stride + pixel] = prev;
-                          I.klistB[(size_t)hi * stride + pixel] = I.klistB[(size_t)(hi - 1) * stride + pixel];
-                          hi--;
-                      }
-                      if (hi < RT64_MAX_HIT_QUERIES) {
-                          I.klistA[(size_t)hi * stride + pixel] = make_uint4(__float_as_uint(key), __float_as_uint(u), __float_as_uint(v), prim);
-                          I.klistB[(size_t)hi * stride + pixel] = make_uint2(__float_as_uint(t), instance);
-                          ++nhits;
-                          if (hi == RT64_MAX_HIT_QUERIES - 1 && t < tmax) tmax = t;      // not IgnoreHit(): the hit is committed
-                      }
-                      if (!(instFlags & GPU_INST_OPAQUE)) return false;
-                  }
-                  const float lim = key + P.maxDepthBias;
-                  if (lim < tmax) tmax = lim;
-                  return false;
-              }, env.cnt);
-    return KLIST ? nhits : (best.hit ? 1u : 0u);
+    a = I.klistA[(size_t)hit * stride + pixel];
+    b = I.klistB[(size_t)hit * stride + pixel];
 }
-
-// Entry `hit` of the list as a shaded record (the any-hit program runs here, on coherent data, instead of during traversal).
-// Reads beyond the 17 allocated slots return an empty record like an out-of-bounds typed UAV load.
-// Entry `hit` of the pixel's sorted list as (instance, primitive, t, u, v), without running the any-hit program.
+// Entry `hit` of the list as (instance, primitive, t, u, v), without running the any-hit program.
 template <bool KLIST>
 DEV bool surface_entry(PRef P, IRef I, size_t pixel, uint32_t hit, const SurfaceHit &best, SurfaceHit &e) {
     if (!KLIST) { e = best; return true; }
     if (hit > RT64_MAX_HIT_QUERIES) return false;
-    const size_t stride = (size_t)P.width * (size_t)P.height;
-    const uint4 a = I.klistA[(size_t)hit * stride + pixel];
-    const uint2 b = I.klistB[(size_t)hit * stride + pixel];
+    uint4 a; uint2 b; klist_slot(P, I, pixel, hit, a, b);
     e.instance = b.y; e.prim = a.w; e.t = __uint_as_float(b.x); e.u = __uint_as_float(a.y); e.v = __uint_as_float(a.z); e.hit = true; e.key = __uint_as_float(a.x);
     return true;
 }
+// Entry `hit` of the list as a shaded record (the any-hit program runs here, on coherent data, instead of during traversal).
 template <bool KLIST>
 DEV bool surface_record(PRef P, IRef I, size_t pixel, uint32_t hit, const SurfaceHit &best, f3 dir,
                         const RayDiff &rayDiff, uint32_t px, uint32_t py, HitRecord &r) {
     if (!KLIST) return surface_anyhit(P, best.instance, best.prim, best.t, best.u, best.v, dir, rayDiff, px, py, r);
     if (hit > RT64_MAX_HIT_QUERIES) return false;
-    const size_t stride = (size_t)P.width * (size_t)P.height;
-    const uint4 a = I.klistA[(size_t)hit * stride + pixel];
-    const uint2 b = I.klistB[(size_t)hit * stride + pixel];
+    uint4 a; uint2 b; klist_slot(P, I, pixel, hit, a, b);
     return surface_anyhit(P, b.y, a.w, __uint_as_float(b.x), __uint_as_float(a.y), __uint_as_float(a.z), dir, rayDiff, px, py, r);
-}
-
-constexpr int TRACE_WAVES = 4;         // waves/SIMD the register allocator must fit for pure-traversal kernels (5 spills, measured no faster)
-// ---- primary visibility --------------------------------------------------------------------------------------------------
-
-template <bool KLIST, bool CACHED = false>
-__global__ __launch_bounds__(RT_BLOCK, KLIST ? 2 : TRACE_WAVES) void primary_trace_kernel(FrameParams Pv, ViewImages Iv, int32_t *hitInstance) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
-    extern __shared__ u32x4_lds dynLds[];
-    if (CACHED) fill_scene_cache(P, dynLds);
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    env.lightIntensity = nullptr; env.lightIndex = nullptr;              // pure visibility: no light is picked in this kernel
-    if (CACHED) env.stk.use_cache(dynLds);
-    uint32_t rays = 0;
-    const uint32_t tiles = tile_count(P);
-    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        PRef P = *kernel_params_here(); IRef I = *kernel_images_here();      // this trip's view of the frame constants and the image table (read where used, never carried across trips)
-        Pixel p = tile_pixel(P, tile);
-        if (!p.valid) continue;
-        f3 o, d; f2 ndc;
-        primary_ray(P, p.x, p.y, o, d, ndc);
-        const size_t i = (size_t)p.y * (size_t)P.width + p.x;
-        RayDiff rayDiff;
-        if (KLIST) {    // the texture-edge any-hit samples with the primary ray differentials (PrimaryRayGen.hlsl:55-59)
-            f3 cU = mk3(P.cameraU[0], P.cameraU[1], P.cameraU[2]), cV = mk3(P.cameraV[0], P.cameraV[1], P.cameraV[2]), cW = mk3(P.cameraW[0], P.cameraW[1], P.cameraW[2]);
-            rayDiff.dOdx = mk3s(0.0f); rayDiff.dOdy = mk3s(0.0f);
-            compute_ray_diffs((cU * ndc.x + cV * ndc.y) + cW, cU, cV, P.resolution[2], P.resolution[3], rayDiff.dDdx, rayDiff.dDdy);
-        }
-        SurfaceHit h;
-        const uint32_t nhits = trace_surface<KLIST, CACHED>(P, env, I, i, o, d, rayDiff, p.x, p.y, h);
-        rays++;
-        uint4 rec;
-        if (KLIST) {
-            I.klistCount[i] = nhits;
-            if (nhits) {
-                const uint4 a = I.klistA[i]; const uint2 b = I.klistB[i];
-                rec = make_uint4(b.x, a.y, a.z, a.w); hitInstance[i] = (int32_t)b.y;
-            }
-            else { rec.x = rec.y = rec.z = rec.w = 0xFFFFFFFFu; hitInstance[i] = -1; }
-        }
-        else if (h.hit) { rec.x = __float_as_uint(h.t); rec.y = __float_as_uint(h.u); rec.z = __float_as_uint(h.v); rec.w = h.prim; hitInstance[i] = (int32_t)h.instance; }
-        else { rec.x = rec.y = rec.z = rec.w = 0xFFFFFFFFu; hitInstance[i] = -1; }
-        reinterpret_cast<uint4 *>(I.primaryHit)[i] = rec;
-    }
-    flush_env(P, env, PASS_PRIMARY_TRACE, CTR_PRIMARY, rays);
 }
 
 // ---- PrimaryRayGen resolve + G-buffer -------------------------------------------------------------------------------------
@@ -422,12 +215,10 @@ DEV void store_primary(PRef P, IRef I, size_t i, int cur, f3 rayDirection, const
 template <bool TRANSPARENT_LIGHT, bool KLIST, bool FULL>
 __global__ __launch_bounds__(RT_BLOCK, SHADE_WAVES) void primary_shade_kernel(FrameParams Pv, ViewImages Iv, const int32_t *hitInstance, int cur) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(false) * RT_BLOCK];
     __shared__ float ldsLightIntensity[(RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     __shared__ uint8_t ldsLightIndex[(RT64_MAX_LIGHTS + 1) * RT_BLOCK];
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    light_columns(env, ldsLightIntensity, ldsLightIndex, RT64_MAX_LIGHTS + 1);
+    ShadeEnv env; shading_env<false>(P, env, ldsStack, ldsLightIntensity, ldsLightIndex, nullptr);
     const uint32_t tiles = tile_count<SHADE_TILE>(P);
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         PRef P = *kernel_params_here(); IRef I = *kernel_images_here();      // this trip's view of the frame constants and the image table (read where used, never carried across trips)
@@ -499,16 +290,6 @@ DEV void compose_lean_pixel(PRef P, IRef I, size_t i, f3 directStored) {
     if (!P.separatePost) store_rgba8(I.final, i, result.x, result.y, result.z, 1.0f);
 }
 
-// CACHED variants of the ray kernels keep the scene cache and the light-selection columns in dynamic LDS:
-//   [scene cache: P.cacheWords x 16 B][light intensities: slots x RT_BLOCK floats][light indices: slots x RT_BLOCK bytes], slots = min(lights, 16) + 1
-DEV uint32_t light_slots(PRef P) { return (P.lightCount < RT64_MAX_LIGHTS ? P.lightCount : (uint32_t)RT64_MAX_LIGHTS) + 1u; }
-DEV void cached_env(PRef P, ShadeEnv &env, u32x4_lds *dynLds) {
-    fill_scene_cache(P, dynLds);
-    env.stk.use_cache(dynLds);
-    float *li = reinterpret_cast<float *>(dynLds + P.cacheWords);
-    light_columns(env, li, reinterpret_cast<uint8_t *>(li + light_slots(P) * blockDim.x), light_slots(P));
-}
-
 // DirectRayGen.hlsl:47-58 for one lit pixel: sampled lights + self light + eye light (before the temporal accumulation).
 template <bool CACHED>
 DEV f3 direct_light_pixel(PRef P, ShadeEnv &env, uint32_t px, uint32_t py, f3 rayDirection, int instanceId, f3 position, f3 normal, f3 specular) {
@@ -526,14 +307,11 @@ DEV f3 direct_light_pixel(PRef P, ShadeEnv &env, uint32_t px, uint32_t py, f3 ra
 template <bool FULL, bool CACHED = false>
 __global__ __launch_bounds__(RT_BLOCK, DIRECT_WAVES) void direct_kernel(FrameParams Pv, ViewImages Iv, int cur) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(CACHED) * RT_BLOCK];
     __shared__ float ldsLightIntensity[CACHED ? 1 : (RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     __shared__ uint8_t ldsLightIndex[CACHED ? 1 : (RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     extern __shared__ u32x4_lds dynLds[];
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    light_columns(env, ldsLightIntensity, ldsLightIndex, RT64_MAX_LIGHTS + 1);
-    if (CACHED) cached_env(P, env, dynLds);
+    ShadeEnv env; shading_env<CACHED>(P, env, ldsStack, ldsLightIntensity, ldsLightIndex, dynLds);
     const uint32_t tiles = tile_count<DIRECT_TILE>(P);
     for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         PRef P = *kernel_params_here(); IRef I = *kernel_images_here();      // this trip's view of the frame constants and the image table (read where used, never carried across trips)
@@ -594,13 +372,10 @@ DEV bool wave_tile_of(uint32_t seq, uint32_t tiles, uint32_t &tileSeq, uint32_t 
 template <bool CACHED, bool FULL, int WAVES, int BLOCK = RT_BLOCK>
 __global__ __launch_bounds__(BLOCK, WAVES) void lean_frame_kernel(FrameParams Pv, ViewImages Iv, int32_t *hitInstance, int cur, int ownedY0, int ownedY1) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(CACHED) * BLOCK];
     // dynamic LDS: [scene cache (CACHED)][light candidates: intensities, indices -- sized by the frame's light count]
     extern __shared__ u32x4_lds dynLds[];
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    if (CACHED) cached_env(P, env, dynLds);
-    else { float *li = reinterpret_cast<float *>(dynLds); light_columns(env, li, reinterpret_cast<uint8_t *>(li + light_slots(P) * BLOCK), light_slots(P)); }
+    ShadeEnv env; shading_env<CACHED, false, BLOCK>(P, env, ldsStack, nullptr, nullptr, dynLds);
     uint32_t rays = 0;
     TraceCounts primaryCnt = TraceCounts();
     const uint32_t tiles = tile_count(P);
@@ -752,12 +527,10 @@ DEV f3 second_bounce_radiance(PRef P, ShadeEnv &env, IRef I, size_t i, uint32_t 
 template <bool KLIST, bool SECOND = false>      // SECOND: extension gi_bounces = 2 (its own instantiation: the reference's one-bounce kernels stay as they were)
 __global__ __launch_bounds__(RT_BLOCK, 3) void indirect_kernel(FrameParams Pv, ViewImages Iv, int cur, int writeFiltered) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(false) * RT_BLOCK];
     __shared__ float ldsLightIntensity[(RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     __shared__ uint8_t ldsLightIndex[(RT64_MAX_LIGHTS + 1) * RT_BLOCK];
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    light_columns(env, ldsLightIntensity, ldsLightIndex, RT64_MAX_LIGHTS + 1);
+    ShadeEnv env; shading_env<false>(P, env, ldsStack, ldsLightIntensity, ldsLightIndex, nullptr);
     uint32_t rays = 0;
     const f3 ambientBase = mk3(P.ambientBaseColor[0], P.ambientBaseColor[1], P.ambientBaseColor[2]);
     const f3 ambient = ambientBase + mk3(P.ambientNoGIColor[0], P.ambientNoGIColor[1], P.ambientNoGIColor[2]);
@@ -899,8 +672,7 @@ DEV f3 bounce_sky_term(PRef P, f3 rayDirection);
 template <bool CACHED>
 __global__ __launch_bounds__(RT_BLOCK, TRACE_WAVES) void bounce_trace_plain_kernel(FrameParams Pv, ViewImages Iv) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(CACHED) * RT_BLOCK];
     __shared__ uint32_t ldsCount[2];
     extern __shared__ u32x4_lds dynLds[];
     const uint32_t tiles = tile_count(P), per = bounce_tiles_per_group(tiles);
@@ -909,9 +681,7 @@ __global__ __launch_bounds__(RT_BLOCK, TRACE_WAVES) void bounce_trace_plain_kern
     if (CACHED) fill_scene_cache(P, dynLds);
     __syncthreads();
     const uint32_t segment = bounce_segment_size(P); const size_t missBase = bounce_miss_base(P, segment);
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    env.lightIntensity = nullptr; env.lightIndex = nullptr;
-    if (CACHED) env.stk.use_cache(dynLds);
+    ShadeEnv env; traversal_env<CACHED>(P, env, ldsStack, dynLds);
     uint32_t rays = 0;
     const size_t stride = (size_t)P.width * (size_t)P.height;
     for (uint32_t k = 0, tile; bounce_tile_of(tiles, per, k, tile); k++) {
@@ -1003,8 +773,7 @@ DEV bool tlas_reaches_a_leaf(PRef P, const f3 &o, const f3 &d, const TraceStack 
 template <bool CACHED>
 __global__ __launch_bounds__(RT_BLOCK, CACHED ? SPLIT_WAVES : TRACE_WAVES) void bounce_trace_split_kernel(FrameParams Pv, ViewImages Iv) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(CACHED) * RT_BLOCK];
     __shared__ uint32_t ldsCount[2];
     __shared__ uint32_t ldsSurvivors;
     __shared__ uint16_t ldsList[SPLIT_ITEMS * RT_BLOCK];
@@ -1016,9 +785,7 @@ __global__ __launch_bounds__(RT_BLOCK, CACHED ? SPLIT_WAVES : TRACE_WAVES) void 
     if (CACHED) fill_scene_cache(P, dynLds);
     __syncthreads();
     const uint32_t segment = bounce_segment_size(P); const size_t missBase = bounce_miss_base(P, segment);
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    env.lightIntensity = nullptr; env.lightIndex = nullptr;
-    if (CACHED) env.stk.use_cache(dynLds);
+    ShadeEnv env; traversal_env<CACHED>(P, env, ldsStack, dynLds);
     uint32_t rays = 0;
     const size_t stride = (size_t)P.width * (size_t)P.height;
     const uint32_t myTiles = blockIdx.x < tiles ? (tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u, items = myTiles * S;
@@ -1106,14 +873,12 @@ __global__ __launch_bounds__(RT_BLOCK, CACHED ? SPLIT_WAVES : TRACE_WAVES) void 
 #define BOUNCE_MIN_LIVE 40
 __global__ __launch_bounds__(RT_BLOCK, TRACE_WAVES) void bounce_trace_refill_kernel(FrameParams Pv, ViewImages Iv) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(false) * RT_BLOCK];
     __shared__ uint32_t ldsCount[2];
     if (threadIdx.x < 2) ldsCount[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t segment = bounce_segment_size(P); const size_t missBase = bounce_miss_base(P, segment);
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    env.lightIntensity = nullptr; env.lightIndex = nullptr;
+    ShadeEnv env; traversal_env<false>(P, env, ldsStack, nullptr);
     uint32_t rays = 0;
     const size_t stride = (size_t)P.width * (size_t)P.height;
     const uint32_t tiles = tile_count(P), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1187,16 +952,13 @@ DEV f3 bounce_sky_term(PRef P, f3 rayDirection) {
 template <bool CACHED, bool SECOND = false>    // SECOND: extension gi_bounces = 2 (its own instantiation: the reference's one-bounce kernel stays as it was)
 __global__ __launch_bounds__(RT_BLOCK, CACHED ? HIT_WAVES : DIRECT_WAVES) void bounce_hit_kernel(FrameParams Pv, ViewImages Iv) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(CACHED) * RT_BLOCK];
     __shared__ float ldsLightIntensity[CACHED ? 1 : (RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     __shared__ uint8_t ldsLightIndex[CACHED ? 1 : (RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     extern __shared__ u32x4_lds dynLds[];
     const uint32_t n = I.bounceCounts[2 * blockIdx.x];      // the segment bounce_trace's workgroup blockIdx.x filled
     if (n == 0) return;                                     // (workgroup-uniform) no hit listed: nothing to shade, no cache fill
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    light_columns(env, ldsLightIntensity, ldsLightIndex, RT64_MAX_LIGHTS + 1);
-    if (CACHED) cached_env(P, env, dynLds);
+    ShadeEnv env; shading_env<CACHED>(P, env, ldsStack, ldsLightIntensity, ldsLightIndex, dynLds);
     const f3 ambientBase = mk3(P.ambientBaseColor[0], P.ambientBaseColor[1], P.ambientBaseColor[2]);
     const f3 ambient = ambientBase + mk3(P.ambientNoGIColor[0], P.ambientNoGIColor[1], P.ambientNoGIColor[2]);
     const uint32_t stride = (uint32_t)P.width * (uint32_t)P.height;
@@ -1328,12 +1090,10 @@ DEV f3 hlsl_refract(f3 i, f3 n, float eta) {
 template <bool KLIST>
 __global__ __launch_bounds__(RT_BLOCK) void refraction_kernel(FrameParams Pv, ViewImages Iv) {
     PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    constexpr uint32_t STACK_WORDS = RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(false) * RT_BLOCK];
     __shared__ float ldsLightIntensity[(RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     __shared__ uint8_t ldsLightIndex[(RT64_MAX_LIGHTS + 1) * RT_BLOCK];
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    light_columns(env, ldsLightIntensity, ldsLightIndex, RT64_MAX_LIGHTS + 1);
+    ShadeEnv env; shading_env<false>(P, env, ldsStack, ldsLightIntensity, ldsLightIndex, nullptr);
     uint32_t rays = 0;
     const f3 ambient = mk3(P.ambientBaseColor[0], P.ambientBaseColor[1], P.ambientBaseColor[2]) + mk3(P.ambientNoGIColor[0], P.ambientNoGIColor[1], P.ambientNoGIColor[2]);
     const uint32_t tiles = tile_count(P);
@@ -1406,14 +1166,11 @@ __global__ __launch_bounds__(RT_BLOCK, CACHED ? REFLECT_WAVES : 1) void reflecti
     if (last && blockIdx.x == 0 && threadIdx.x < 4) I.reflectFlags[(parity ^ 1) * 4 + threadIdx.x] = 0;
     if (pass > 0 && pass < 4 && I.reflectFlags[parity * 4 + pass] == 0u) return;          // (workgroup-uniform: written by the launch before this one; passes beyond the fourth always scan)
     const uint32_t frameTag = P.frameCount + 1u;       // marks the continuation state this frame wrote (never 0: the images start zeroed)
-    constexpr uint32_t STACK_WORDS = CACHED ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS;
-    __shared__ uint32_t ldsStack[STACK_WORDS * RT_BLOCK];
+    __shared__ uint32_t ldsStack[stack_words(CACHED) * RT_BLOCK];
     __shared__ float ldsLightIntensity[CACHED ? 1 : (RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     __shared__ uint8_t ldsLightIndex[CACHED ? 1 : (RT64_MAX_LIGHTS + 1) * RT_BLOCK];
     extern __shared__ u32x4_lds dynLds[];
-    ShadeEnv env; env.stk = make_stack(P, ldsStack, STACK_WORDS); env.cnt = TraceCounts(); env.shadowRays = 0;
-    light_columns(env, ldsLightIntensity, ldsLightIndex, RT64_MAX_LIGHTS + 1);
-    if (CACHED) cached_env(P, env, dynLds);
+    ShadeEnv env; shading_env<CACHED>(P, env, ldsStack, ldsLightIntensity, ldsLightIndex, dynLds);
     uint32_t rays = 0;
     const f3 ambient = mk3(P.ambientBaseColor[0], P.ambientBaseColor[1], P.ambientBaseColor[2]) + mk3(P.ambientNoGIColor[0], P.ambientNoGIColor[1], P.ambientNoGIColor[2]);
     const uint32_t tiles = tile_count(P);
@@ -1497,369 +1254,21 @@ __global__ __launch_bounds__(RT_BLOCK, CACHED ? REFLECT_WAVES : 1) void reflecti
     flush_env(P, env, PASS_REFLECTION, CTR_REFLECTION, rays);
 }
 
-// ---- GaussianFilterRGB3x3CS ------------------------------------------------------------------------------------------------
-
-DEV f3 bilinear_clamp_rgb(const uint16_t *img, int w, int h, float u, float v) {   // LINEAR + CLAMP static sampler, rt64_device.cpp:737-742
-    float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
-    float x0f = floorf(x), y0f = floorf(y), fx = x - x0f, fy = y - y0f;
-    int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-    x0 = x0 < 0 ? 0 : (x0 >= w ? w - 1 : x0); x1 = x1 < 0 ? 0 : (x1 >= w ? w - 1 : x1);
-    y0 = y0 < 0 ? 0 : (y0 >= h ? h - 1 : y0); y1 = y1 < 0 ? 0 : (y1 >= h ? h - 1 : y1);
-    f3 c00 = xyz(load_rgba16f(img, (size_t)y0 * w + x0)), c10 = xyz(load_rgba16f(img, (size_t)y0 * w + x1));
-    f3 c01 = xyz(load_rgba16f(img, (size_t)y1 * w + x0)), c11 = xyz(load_rgba16f(img, (size_t)y1 * w + x1));
-    f3 top = lerp3(c00, c10, fx), bot = lerp3(c01, c11, fx);
-    return lerp3(top, bot, fy);
-}
-
-__global__ __launch_bounds__(256) void gaussian_kernel(const uint16_t *in, uint16_t *out, int w, int h, int y0, int y1) {
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= w || y >= y1) return;
-    const float texelX = 1.0f / (float)w, texelY = 1.0f / (float)h;
-    const float k00 = 0.077847f, k01 = 0.123317f, k11 = 0.195346f;
-    float wt[4];
-    const bool xl = x == 0, xr = x == w - 1, yt = y == 0, yb = y == h - 1;
-    if (x > 0 && y > 0 && x < w - 1 && y < h - 1) { wt[0] = k00 + k01 + k01 + k11; wt[1] = k00 + k01; wt[2] = k00 + k01; wt[3] = k00; }
-    else if (xl && yt) { wt[0] = k11 / 0.519827f; wt[1] = k01 / 0.519827f; wt[2] = k01 / 0.519827f; wt[3] = k00 / 0.519827f; }
-    else if (xr && yt) { wt[0] = (k01 + k11) / 0.519827f; wt[1] = 0.0f; wt[2] = 0.201164f / 0.519827f; wt[3] = 0.0f; }
-    else if (xl && yb) { wt[0] = (k01 + k11) / 0.519827f; wt[1] = (k00 + k01) / 0.519827f; wt[2] = 0.0f; wt[3] = 0.0f; }
-    else if (xr && yb) { wt[0] = (k00 + k01 + k01 + k11) / 0.519827f; wt[1] = wt[2] = wt[3] = 0.0f; }
-    else if (xl) { wt[0] = (k01 + k11) / 0.720991f; wt[1] = (k00 + k01) / 0.720991f; wt[2] = k01 / 0.720991f; wt[3] = k00 / 0.720991f; }
-    else if (xr) { wt[0] = (k00 + k01 + k01 + k11) / 0.720991f; wt[1] = 0.0f; wt[2] = (k00 + k01) / 0.720991f; wt[3] = 0.0f; }
-    else if (yt) { wt[0] = (k01 + k11) / 0.720991f; wt[1] = k01 / 0.720991f; wt[2] = (k00 + k01) / 0.720991f; wt[3] = k00 / 0.720991f; }
-    else { wt[0] = (k00 + k01 + k01 + k11) / 0.720991f; wt[1] = (k00 + k01) / 0.720991f; wt[2] = 0.0f; wt[3] = 0.0f; }
-    const float off[3][2] = { { 0.5f + -k01 / (k01 + k11), 0.5f + -k01 / (k01 + k11) }, { 0.5f + 1.0f, 0.5f + -k00 / (k00 + k01) }, { 0.5f + -k00 / (k00 + k01), 0.5f + 1.0f } };
-    f3 smp[4];
-#pragma unroll
-    for (int k = 0; k < 3; k++) smp[k] = bilinear_clamp_rgb(in, w, h, ((float)x + off[k][0]) * texelX, ((float)y + off[k][1]) * texelY);
-    smp[3] = (x + 1 < w && y + 1 < h) ? xyz(load_rgba16f(in, (size_t)(y + 1) * w + (x + 1))) : mk3s(0.0f);
-    const size_t i = (size_t)y * w + x;
-    f4 old = load_rgba16f(out, i);
-    store_rgba16f(out, i, smp[0].x * wt[0] + smp[1].x * wt[1] + smp[2].x * wt[2] + smp[3].x * wt[3],
-                  smp[0].y * wt[0] + smp[1].y * wt[1] + smp[2].y * wt[2] + smp[3].y * wt[3],
-                  smp[0].z * wt[0] + smp[1].z * wt[1] + smp[2].z * wt[2] + smp[3].z * wt[3], old.w);
-}
-
-// ---- ComposePS + PostProcessPS (fused) -------------------------------------------------------------------------------------
-
-// LEAN: direct light straight from the raw accumulation, constant ambient for the indirect term (giSamples == 0), and no
-// reflection / refraction / transparent reads -- all of them are exact zeros on a lean frame.
-template <bool LEAN>
-__global__ __launch_bounds__(256) void compose_post_kernel(FrameParams Pv, ViewImages Iv, int cur, int writeFinal) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = P.tileY0 + blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= P.width || y >= P.tileY1 || !row_owned(P, y)) return;
-    const size_t i = (size_t)y * (size_t)P.width + x;
-    f4 d = load_rgba8(I.diffuse, i);
-    f3 result;
-    if (d.w > RT_EPSILON) {
-        f3 diffuse = xyz(d);
-        f3 direct, indirect;
-        if (LEAN) {
-            direct = xyz(load_rgba16f(I.directLight[cur], i));
-            indirect = mk3(q_f16(P.ambientBaseColor[0] + P.ambientNoGIColor[0]), q_f16(P.ambientBaseColor[1] + P.ambientNoGIColor[1]), q_f16(P.ambientBaseColor[2] + P.ambientNoGIColor[2]));
-        }
-        else { direct = xyz(load_rgba16f(I.filteredDirect[1], i)); indirect = xyz(load_rgba16f(I.filteredIndirect[1], i)); }
-        result = diffuse * (direct + indirect);
-        result = lerp3(diffuse, result, d.w);
-        if (!LEAN) {
-            result = result + xyz(load_rgba16f(I.reflection, i));
-            result = result + xyz(load_rgba16f(I.refraction, i));
-            result = result + xyz(load_rgba16f(I.transparent, i));
-        }
-    }
-    else result = xyz(d);
-    reinterpret_cast<float4 *>(I.output)[i] = make_float4(result.x, result.y, result.z, 1.0f);
-    if (!P.separatePost && writeFinal) store_rgba8(I.final, i, result.x, result.y, result.z, 1.0f);   // PostProcessPS passthrough (motionBlurStrength == 0, render size == screen size)
-}
-
-// Longest-first order of the one-kernel frame's tiles (device option tile_order; scenes that walk from HBM): tiles sorted by the cost the frame just recorded, most
-// expensive first -- a counting sort over min(cost, 1023) in one workgroup (a 1080p frame has 8 160 tiles) -- and the costs cleared for the next frame.  Ties land in
-// whatever order the atomics resolve: any permutation renders the same picture.
-__global__ __launch_bounds__(1024) void tile_order_kernel(uint32_t *cost, uint32_t *order, uint32_t n) {
-    __shared__ uint32_t bucket[1024];
-    bucket[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += 1024) atomicAdd(&bucket[1023u - min(cost[i], 1023u)], 1u);
-    __syncthreads();
-    // exclusive scan of the 1024 counts: a wave scans its 64, then the 16 wave totals are added up by every thread
-    const uint32_t mine = bucket[threadIdx.x];
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64); if ((threadIdx.x & 63u) >= (uint32_t)d) incl += up; }
-    __shared__ uint32_t waveTotal[16];
-    if ((threadIdx.x & 63u) == 63u) waveTotal[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) base += waveTotal[w];
-    bucket[threadIdx.x] = base + incl - mine;
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += 1024) {
-        const uint32_t b = 1023u - min(cost[i], 1023u);
-        order[atomicAdd(&bucket[b], 1u)] = i;
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += 1024) cost[i] = 0;
-}
-
-// Extension primary_spp (rule P3, oracle/oracle_render.c): rtOutput of sub-frame `sub` added to the running sum of the frame's sub-frames, in order; the last
-// sub-frame turns the sum into the mean (one multiplication by 1.0f / count), stores it as rtOutput and its PostProcessPS passthrough as the back buffer.
-__global__ __launch_bounds__(256) void spp_accumulate_kernel(FrameParams Pv, ViewImages Iv, float4 *sum, int sub, int count) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = P.tileY0 + blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= P.width || y >= P.tileY1 || !row_owned(P, y)) return;
-    const size_t i = (size_t)y * (size_t)P.width + x;
-    float4 v = reinterpret_cast<const float4 *>(I.output)[i];
-    if (sub > 0) { const float4 a = sum[i]; v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w; }
-    if (sub + 1 < count) { sum[i] = v; return; }
-    const float inv = 1.0f / (float)count;
-    v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
-    reinterpret_cast<float4 *>(I.output)[i] = v;
-    store_rgba8(I.final, i, v.x, v.y, v.z, 1.0f);
-}
-
-// PostProcessPS.hlsl:13-36 as its own pass: the screen-size back buffer resampled from the render-size output with the static
-// sampler of rt64_device.cpp:958-973 (MIN_MAG_MIP_LINEAR, WRAP), plus the motion-blur gather along gFlow.  Only launched when
-// the render size differs from the screen size (RT64_VIEW_DESC.resolutionScale) or motionBlurStrength > 0.
-DEV int wrapi(int i, int n) { int j = i % n; return j < 0 ? j + n : j; }
-DEV f4 sample_output_linear_wrap(const float *img, int w, int h, float u, float v) {
-    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
-    const float x0f = floorf(x), y0f = floorf(y), fx = x - x0f, fy = y - y0f;
-    const int x0 = wrapi((int)x0f, w), x1 = wrapi((int)x0f + 1, w), y0 = wrapi((int)y0f, h), y1 = wrapi((int)y0f + 1, h);
-    const float4 c00 = reinterpret_cast<const float4 *>(img)[(size_t)y0 * w + x0], c10 = reinterpret_cast<const float4 *>(img)[(size_t)y0 * w + x1];
-    const float4 c01 = reinterpret_cast<const float4 *>(img)[(size_t)y1 * w + x0], c11 = reinterpret_cast<const float4 *>(img)[(size_t)y1 * w + x1];
-    f4 r;
-    { const float top = c00.x + fx * (c10.x - c00.x), bot = c01.x + fx * (c11.x - c01.x); r.x = top + fy * (bot - top); }
-    { const float top = c00.y + fx * (c10.y - c00.y), bot = c01.y + fx * (c11.y - c01.y); r.y = top + fy * (bot - top); }
-    { const float top = c00.z + fx * (c10.z - c00.z), bot = c01.z + fx * (c11.z - c01.z); r.z = top + fy * (bot - top); }
-    r.w = 1.0f;
-    return r;
-}
-DEV f2 sample_flow_linear_wrap(const uint16_t *img, int w, int h, float u, float v) {
-    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
-    const float x0f = floorf(x), y0f = floorf(y), fx = x - x0f, fy = y - y0f;
-    const int x0 = wrapi((int)x0f, w), x1 = wrapi((int)x0f + 1, w), y0 = wrapi((int)y0f, h), y1 = wrapi((int)y0f + 1, h);
-    auto ld = [&](int xx, int yy) { const uint32_t p = reinterpret_cast<const uint32_t *>(img)[(size_t)yy * w + xx]; f2 r; r.x = f16_bits_to_f32((uint16_t)(p & 0xFFFFu)); r.y = f16_bits_to_f32((uint16_t)(p >> 16)); return r; };
-    const f2 c00 = ld(x0, y0), c10 = ld(x1, y0), c01 = ld(x0, y1), c11 = ld(x1, y1);
-    f2 r;
-    { const float top = c00.x + fx * (c10.x - c00.x), bot = c01.x + fx * (c11.x - c01.x); r.x = top + fy * (bot - top); }
-    { const float top = c00.y + fx * (c10.y - c00.y), bot = c01.y + fx * (c11.y - c01.y); r.y = top + fy * (bot - top); }
-    return r;
-}
-// Viewport + scissor of the full-screen triangle: the screen, or the rectangles of the first ray-traced instance (rt64_view.cpp:1258-1271,1624-1626).
-// False: pixel (x, y) of the back buffer is outside them; otherwise (u, v) is the FullScreenVS interpolant at the pixel centre.
-DEV bool full_screen_uv(PRef P, int x, int y, float &u, float &v) {
-    const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
-    if (x < P.rtScissor[0] || x >= P.rtScissor[2] || y < P.rtScissor[1] || y >= P.rtScissor[3]) return false;
-    if (!(cx >= P.rtViewport[0]) || !(cx < P.rtViewport[0] + P.rtViewport[2]) || !(cy >= P.rtViewport[1]) || !(cy < P.rtViewport[1] + P.rtViewport[3])) return false;
-    u = (cx - P.rtViewport[0]) / P.rtViewport[2]; v = (cy - P.rtViewport[1]) / P.rtViewport[3];
-    return true;
-}
-__global__ __launch_bounds__(256) void post_process_kernel(FrameParams Pv, ViewImages Iv) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    const int sw = (int)P.resolution[2], sh = (int)P.resolution[3];
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= sw || y >= sh) return;
-    float u, v;
-    if (!full_screen_uv(P, x, y, u, v)) return;
-    f4 color; bool blurred = false;
-    if (P.motionBlurStrength > 0.0f && P.motionBlurSamples > 0) {
-        const f2 fl = sample_flow_linear_wrap(I.flow, P.width, P.height, u, v);
-        const float flx = fl.x / P.resolution[0], fly = fl.y / P.resolution[1];
-        const float flowLength = sqrtf(flx * flx + fly * fly);
-        if (flowLength > 1e-6f) {
-            const float sampleStep = P.motionBlurStrength / (float)P.motionBlurSamples;
-            float sr = 0.0f, sg = 0.0f, sb = 0.0f, sumWeight = 0.0f;
-            const float su = u - (flx * P.motionBlurStrength / 2.0f), sv = v - (fly * P.motionBlurStrength / 2.0f);
-            for (uint32_t k = 0; k < P.motionBlurSamples; k++) {
-                float uu = su + flx * (float)k * sampleStep, vv = sv + fly * (float)k * sampleStep;
-                uu = fminf(fmaxf(uu, 0.0f), 1.0f); vv = fminf(fmaxf(vv, 0.0f), 1.0f);
-                const f4 c = sample_output_linear_wrap(P.postSource, P.postSourceW, P.postSourceH, uu, vv);
-                sr += c.x * 1.0f; sg += c.y * 1.0f; sb += c.z * 1.0f; sumWeight += 1.0f;
-            }
-            color = mk4(sr / sumWeight, sg / sumWeight, sb / sumWeight, 1.0f);
-            blurred = true;
-        }
-    }
-    if (!blurred) color = sample_output_linear_wrap(P.postSource, P.postSourceW, P.postSourceH, u, v);
-    store_rgba8(I.final, (size_t)y * (size_t)sw + x, color.x, color.y, color.z, 1.0f);
-}
-
-// One pixel of the debug view's image in its storage format (DebugSource::kind / srcBytes); single-channel images in .x, 32-bit words as their bits.
-DEV f4 debug_load(const DebugSource &src, size_t i) {
-    if (src.kind == 1) {
-        if (src.srcBytes == 8) return load_rgba16f(static_cast<const uint16_t *>(src.ptr), i);
-        const uint32_t h = static_cast<const uint32_t *>(src.ptr)[i];                                    // RG16F (flow)
-        return mk4(f16_bits_to_f32((uint16_t)(h & 0xFFFFu)), f16_bits_to_f32((uint16_t)(h >> 16)), 0.0f, 0.0f);
-    }
-    if (src.kind == 2) {
-        if (src.srcBytes == 4) return load_rgba8(static_cast<const uint8_t *>(src.ptr), i);
-        return mk4(from_unorm8(static_cast<const uint8_t *>(src.ptr)[i]), 0.0f, 0.0f, 0.0f);               // R8 masks
-    }
-    if (src.srcBytes == 16) { const float4 p = static_cast<const float4 *>(src.ptr)[i]; return mk4(p.x, p.y, p.z, p.w); }
-    return mk4(__uint_as_float(static_cast<const uint32_t *>(src.ptr)[i]), 0.0f, 0.0f, 0.0f);           // instance id / depth
-}
-// DebugPS.hlsl:47-157 in PostProcess's place (device option visualization_mode; rt64_view.cpp:1628-1650): the texel uint2(uv * resolution.xy) of the image the mode
-// names -- nearest, zeros out of range -- shown as DebugPS shows it and blended over the back buffer the background pass left (alphaBlendDesc, rt64_device.cpp:532-538:
-// SRC_ALPHA / INV_SRC_ALPHA, alpha ONE / INV_SRC_ALPHA, the source clamped to [0, 1] like a UNORM target clamps it).  The mode is uniform over the launch.
-__global__ __launch_bounds__(256) void debug_view_kernel(FrameParams Pv, ViewImages Iv, DebugSource src) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv;
-    const int sw = (int)P.resolution[2], sh = (int)P.resolution[3];
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= sw || y >= sh) return;
-    if (!P.separatePost && (y < P.tileY0 || y >= P.tileY1 || !row_owned(P, y))) return;     // back-buffer rows are render rows: this device's only
-    float u, v;
-    if (!full_screen_uv(P, x, y, u, v)) return;
-    const float px = u * P.resolution[0], py = v * P.resolution[1];
-    const uint32_t w = (uint32_t)P.width, h = (uint32_t)P.height;
-    auto texel = [&](uint32_t tx, uint32_t ty) { return tx < w && ty < h ? debug_load(src, (size_t)ty * w + tx) : mk4(0.0f, 0.0f, 0.0f, 0.0f); };
-    f4 c;
-    if (src.mode == RT64_IMAGE_FLOW) {
-        // getMotionVector: a 1-pixel line from the centre of the pixel's 32 x 32 block along the flow found there (distanceFromLineSegment < 1)
-        const float sx = floorf(px / 32.0f) * 32.0f + 16.0f, sy = floorf(py / 32.0f) * 32.0f + 16.0f;
-        const f4 fl = texel((uint32_t)rintf(sx), (uint32_t)rintf(sy));
-        const float ex = sx + fl.x, ey = sy + fl.y;
-        const float len = sqrtf((sx - ex) * (sx - ex) + (sy - ey) * (sy - ey)), l2 = len * len;
-        float dist;
-        if (l2 == 0.0f) dist = sqrtf((px - sx) * (px - sx) + (py - sy) * (py - sy));
-        else {
-            const float t = fmaxf(0.0f, fminf(1.0f, ((px - sx) * (ex - sx) + (py - sy) * (ey - sy)) / l2));
-            const float qx = sx + t * (ex - sx), qy = sy + t * (ey - sy);
-            dist = sqrtf((px - qx) * (px - qx) + (py - qy) * (py - qy));
-        }
-        c = dist < 1.0f ? mk4(1.0f, 1.0f, 1.0f, 1.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    else {
-        const uint32_t tx = (uint32_t)px, ty = (uint32_t)py;
-        c = texel(tx, ty);
-        // the G-buffer after the reflection passes: their continuation state where they tagged the pixel (apply_reflection_state_kernel, without the write)
-        if (src.reflTag && tx < w && ty < h && I.reflTag[(size_t)ty * w + tx] == src.reflTag) {
-            const size_t i = (size_t)ty * w + tx;
-            const uint4 s0 = I.reflState0[i], s1 = I.reflState1[i];
-            if (src.mode == RT64_IMAGE_SHADING_POSITION) c = mk4(__uint_as_float(s0.x), __uint_as_float(s0.y), __uint_as_float(s0.z), 0.0f);
-            else if (src.mode == RT64_IMAGE_SHADING_NORMAL) c = unpack_rgba16f_bits(s1.z, s1.w);
-            else c.x = __uint_as_float(s0.w);
-        }
-        switch (src.mode) {
-        case RT64_IMAGE_SHADING_NORMAL: c = mk4((c.x + 1.0f) / 2.0f, (c.y + 1.0f) / 2.0f, (c.z + 1.0f) / 2.0f, 1.0f); break;
-        case RT64_IMAGE_INSTANCE_ID: {          // getInstanceId: a colour per instance, nothing on a miss
-            const int32_t id = (int32_t)__float_as_uint(c.x);
-            if (id < 0) { c = mk4(0.0f, 0.0f, 0.0f, 0.0f); break; }
-            uint32_t seed = init_rand((uint32_t)id, 0, 16);
-            const float r = next_rand(seed), g = next_rand(seed), b = next_rand(seed);
-            c = mk4(r, g, b, 1.0f);
-            break;
-        }
-        case RT64_IMAGE_REACTIVE_MASK: case RT64_IMAGE_LOCK_MASK: case RT64_IMAGE_DEPTH: c = mk4(c.x, c.x, c.x, 1.0f); break;
-        default: c.w = 1.0f;
-        }
-    }
-    auto unorm = [](float a) { return a > 0.0f ? fminf(a, 1.0f) : 0.0f; };
-    const float r = unorm(c.x), g = unorm(c.y), b = unorm(c.z), a = unorm(c.w), ia = 1.0f - a;
-    const size_t i = (size_t)y * (size_t)sw + x;
-    const f4 d = load_rgba8(I.final, i);
-    store_rgba8(I.final, i, r * a + d.x * ia, g * a + d.y * ia, b * a + d.z * ia, a + d.w * ia);
-}
-
-// IndirectRayGen with giSamples == 0 (IndirectRayGen.hlsl:135): every pixel gets ambientBase + ambientNoGI, history 0.
-__global__ __launch_bounds__(256) void indirect_constant_kernel(FrameParams Pv, ViewImages Iv, int cur) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = P.tileY0 + blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= P.width || y >= P.tileY1 || !row_owned(P, y)) return;
-    const size_t i = (size_t)y * (size_t)P.width + x;
-    const float r = P.ambientBaseColor[0] + P.ambientNoGIColor[0], g = P.ambientBaseColor[1] + P.ambientNoGIColor[1], b = P.ambientBaseColor[2] + P.ambientNoGIColor[2];
-    store_rgba16f(I.indirectLight[cur], i, r, g, b, 0.0f);
-    store_rgba16f(I.filteredIndirect[1], i, r, g, b, 0.0f);
-}
-
-// The reflection passes keep their continuation state beside the G-buffer (ViewImages::reflState0 / 1); the reference rewrites the G-buffer itself
-// (ReflectionRayGen.hlsl:117-124).  A reader of gShadingPosition / gViewDirection / gShadingNormal / gInstanceId gets the reference's bytes through this
-// kernel: every pixel the frame's passes tagged takes its last state (View::applyReflectionState, on readback only).
-__global__ __launch_bounds__(256) void apply_reflection_state_kernel(ViewImages I, int width, int y0, int y1, uint32_t frameTag) {
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = y0 + blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= width || y >= y1) return;
-    const size_t i = (size_t)y * (size_t)width + x;
-    if (I.reflTag[i] != frameTag) return;
-    const uint4 s0 = I.reflState0[i], s1 = I.reflState1[i];
-    reinterpret_cast<float4 *>(I.shadingPosition)[i] = make_float4(__uint_as_float(s0.x), __uint_as_float(s0.y), __uint_as_float(s0.z), 0.0f);
-    reinterpret_cast<uint2 *>(I.viewDirection)[i] = make_uint2(s1.x, s1.y);
-    reinterpret_cast<uint2 *>(I.shadingNormal)[i] = make_uint2(s1.z, s1.w);
-    I.instanceId[i] = (int32_t)s0.w;
-}
-
-__global__ __launch_bounds__(256) void clear_final_kernel(FrameParams Pv, ViewImages Iv) {
-    PRef P = *kernel_params(); IRef I = *kernel_images(); (void)Pv; (void)Iv; (void)I;
-    if (P.separatePost) {         // the back buffer has the screen size, the frame is not partitioned
-        const int sw = (int)P.resolution[2], sh = (int)P.resolution[3];
-        const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
-        if (x < sw && y < sh) store_rgba8(I.final, (size_t)y * (size_t)sw + x, 0.0f, 0.0f, 0.0f, 1.0f);
-        return;
-    }
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = P.tileY0 + blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= P.width || y >= P.tileY1 || !row_owned(P, y)) return;
-    store_rgba8(I.final, (size_t)y * (size_t)P.width + x, 0.0f, 0.0f, 0.0f, 1.0f);   // cleared back buffer, rt64_device.cpp:996-997
-}
-
 }  // namespace
 
-#ifndef RT_ASSUME_SIMPLE
-// One spill slab per lane of every workgroup of the largest grid a frame of `width` x `rows` can launch: the persistent kernels use
-// at most RT_GRID_BLOCKS workgroups, the one-kernel frame one per 16 x 16 tile.
-size_t rt_stack_spill_bytes(int width, int rows) {
-    const size_t tiles = (size_t)((width + 15) / 16) * (size_t)((rows + 15) / 16);
-    size_t blocks = tiles > (size_t)RT_GRID_BLOCKS ? tiles : (size_t)RT_GRID_BLOCKS;
-    if (blocks > RT_MAX_FRAME_GROUPS) blocks = RT_MAX_FRAME_GROUPS;
-    blocks += 8;          // the per-wave frame rounds its grid up to whole groups of 8 tiles (32 one-wave workgroups)       // no launch has more workgroups than that (launch_lean_frame, sparse_grid)
-    return blocks * RT_BLOCK * (RT_STACK_SPILL_HEADER + RT_STACK_SPILL) * sizeof(uint32_t);      // (a lane's entries + the header in front of them: trace.h)
-}
-// Host side of tile_count: the 16-row strips stripRank, stripRank + stripCount, ... of [tileY0, tileY1) are this device's.
-unsigned owned_tiles(const FrameParams &P, bool rowTiles) {
-    const unsigned all = (unsigned)(P.tileY1 - P.tileY0 + 15) / 16;
-    const unsigned strips = all > (unsigned)P.stripRank ? (all - (unsigned)P.stripRank + (unsigned)P.stripCount - 1) / (unsigned)P.stripCount : 0u;
-    return rowTiles ? (unsigned)((P.width + 31) / 32) * strips * 2u : (unsigned)((P.width + 15) / 16) * strips;
-}
-#endif
-
-
-// Grid of a ray kernel: one persistent workgroup per CU slot (RT_GRID_BLOCKS), or one per tile when the device's share of the
-// frame has fewer tiles than that (small frames, a 1/8 strip share): workgroups without a tile only cost launch time.
-static unsigned rt_grid(const FrameParams &P) {
-    const unsigned tiles = owned_tiles(P, true);          // (never fewer than the 16 x 16 tiles: two 32 x 8 tiles per 32 columns of a strip)
-    return tiles < 1u ? 1u : (tiles < (unsigned)RT_GRID_BLOCKS ? tiles : (unsigned)RT_GRID_BLOCKS);
-}
-#define LAUNCH_RAY(kernel, ...) do { hipLaunchKernelGGL(kernel, dim3(rt_grid(P)), dim3(RT_BLOCK), 0, s, __VA_ARGS__); return hipGetLastError(); } while (0)
-// dynamic LDS of a CACHED kernel: scene cache, plus the light-selection columns when the kernel picks lights
-static size_t cached_lds_bytes(const FrameParams &P, bool lights) {
-    const size_t slots = (P.lightCount < RT64_MAX_LIGHTS ? P.lightCount : (uint32_t)RT64_MAX_LIGHTS) + 1u;
-    return (size_t)P.cacheWords * 16 + (lights ? (slots * RT_BLOCK * 5 + 15) / 16 * 16 : 0);
-}
-#define LAUNCH_RAY_LDS(kernel, bytes, ...) do { hipLaunchKernelGGL(kernel, dim3(rt_grid(P)), dim3(RT_BLOCK), bytes, s, __VA_ARGS__); return hipGetLastError(); } while (0)
-
-#ifndef RT_ASSUME_SIMPLE
-hipError_t launch_scene_cache_image(const GpuInstance *instances, const uint32_t *tlasIndex, const GpuNode *tlasNodes, uint32_t cacheInstances, void *image, bool blasOnly, hipStream_t s) {
-    hipLaunchKernelGGL(scene_cache_image_kernel, dim3(1), dim3(RT_BLOCK), 0, s, instances, tlasIndex, tlasNodes, cacheInstances, static_cast<u32x4 *>(image), blasOnly ? 1 : 0);
-    return hipGetLastError();
-}
-hipError_t launch_primary_trace(const FrameParams &P, const ViewImages &I, int32_t *hitInstance, bool klist, hipStream_t s) {
-    if (klist) LAUNCH_RAY(primary_trace_kernel<true>, P, I, hitInstance);
-    if (P.cacheWords) LAUNCH_RAY_LDS((primary_trace_kernel<false, true>), cached_lds_bytes(P, false), P, I, hitInstance);
-    LAUNCH_RAY(primary_trace_kernel<false>, P, I, hitInstance);
-}
-#endif
-
+// The launchers.  A kernel's template arguments come from runtime flags through with_flag (pass_common.h) wherever every combination exists; the kernels that
+// exist in three of four combinations keep an if chain, so that no kernel is built that nothing starts.
 hipError_t RT_LAUNCHER(launch_primary_shade)(const FrameParams &P, const ViewImages &I, const int32_t *hitInstance, int cur, bool transparentLighting, bool lean, hipStream_t s) {
     RT_ROUTE_SIMPLE(launch_primary_shade_simple(P, I, hitInstance, cur, transparentLighting, lean, s));
-    if (transparentLighting) LAUNCH_RAY((primary_shade_kernel<true, true, true>), P, I, hitInstance, cur);
-    if (lean) LAUNCH_RAY((primary_shade_kernel<false, false, false>), P, I, hitInstance, cur);
-    LAUNCH_RAY((primary_shade_kernel<false, false, true>), P, I, hitInstance, cur);
+    if (transparentLighting) return launch(primary_shade_kernel<true, true, true>, rt_grid(P), RT_BLOCK, 0, s, P, I, hitInstance, cur);
+    if (lean) return launch(primary_shade_kernel<false, false, false>, rt_grid(P), RT_BLOCK, 0, s, P, I, hitInstance, cur);
+    return launch(primary_shade_kernel<false, false, true>, rt_grid(P), RT_BLOCK, 0, s, P, I, hitInstance, cur);
 }
 hipError_t RT_LAUNCHER(launch_direct)(const FrameParams &P, const ViewImages &I, int cur, bool lean, hipStream_t s) {
     RT_ROUTE_SIMPLE(launch_direct_simple(P, I, cur, lean, s));
-    if (P.cacheWords) {
-        if (lean) LAUNCH_RAY_LDS((direct_kernel<false, true>), cached_lds_bytes(P, true), P, I, cur);
-        LAUNCH_RAY_LDS((direct_kernel<true, true>), cached_lds_bytes(P, true), P, I, cur);
-    }
-    if (lean) LAUNCH_RAY(direct_kernel<false>, P, I, cur);
-    LAUNCH_RAY(direct_kernel<true>, P, I, cur);
+    return with_flag(!lean, [&](auto FULL) { return with_flag(P.cacheWords != 0, [&](auto CACHED) {
+        return launch(direct_kernel<decltype(FULL)::value, decltype(CACHED)::value>, rt_grid(P), RT_BLOCK, CACHED ? cached_lds_bytes(P, true) : 0, s, P, I, cur);
+    }); });
 }
 // One workgroup per tile: the hardware dispatcher hands the next tile to whichever CU has a free slot (LEAN_WAVES workgroups per
 // CU), which together with the bottom-up tile order (geometry first) is a longest-job-first schedule; a resident round of
@@ -1871,30 +1280,30 @@ hipError_t RT_LAUNCHER(launch_lean_frame)(const FrameParams &P, const ViewImages
     // ... up to 8192 workgroups; bigger frames give every workgroup ceil(tiles / 8192) tiles (round-robin, same bottom-up order), which
     // amortises the scene-cache fill again (1440p: 2 tiles per workgroup, 4K: 4)
     if (maxGroups < 1u || maxGroups > RT_MAX_FRAME_GROUPS) maxGroups = RT_MAX_FRAME_GROUPS;
+    unsigned grid; size_t lds = cached_lds_bytes(P, true);       // the scene cache + the light-candidate columns of this frame's light count
     if (P.cacheWords) {
-        const size_t lds = cached_lds_bytes(P, true);       // the scene cache + the light-candidate columns of this frame's light count
-        const unsigned perGroup = (tiles + maxGroups - 1u) / maxGroups, grid = tiles < 1u ? 1u : (tiles + perGroup - 1u) / perGroup;
-        if (full) hipLaunchKernelGGL((lean_frame_kernel<true, true, LEAN_WAVES>), dim3(grid), dim3(RT_BLOCK), lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
-        else hipLaunchKernelGGL((lean_frame_kernel<true, false, LEAN_WAVES>), dim3(grid), dim3(RT_BLOCK), lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
+        const unsigned perGroup = (tiles + maxGroups - 1u) / maxGroups;
+        grid = tiles < 1u ? 1u : (tiles + perGroup - 1u) / perGroup;
     }
     else {
         // one wave per workgroup: trips = 32 per 8 tiles (wave_tile_of), up to 4 x maxGroups workgroups, a multiple of 32 so that every trip of a workgroup stays on its XCD's tiles
         const unsigned trips = ((tiles + 7u) / 8u) * 32u, cap = maxGroups * 4u, perGroup = (trips + cap - 1u) / cap;
-        unsigned grid = trips < 1u ? 32u : (trips + perGroup - 1u) / perGroup;
+        grid = trips < 1u ? 32u : (trips + perGroup - 1u) / perGroup;
         grid = (grid + 31u) / 32u * 32u;
-        const size_t ldsWave = cached_lds_bytes(P, true) / (RT_BLOCK / 64) + 16;      // the light-candidate columns of one wave
-        if (full) hipLaunchKernelGGL((lean_frame_kernel<false, true, LEAN_WAVES, 64>), dim3(grid), dim3(64), ldsWave, s, P, I, hitInstance, cur, ownedY0, ownedY1);
-        else hipLaunchKernelGGL((lean_frame_kernel<false, false, LEAN_WAVES, 64>), dim3(grid), dim3(64), ldsWave, s, P, I, hitInstance, cur, ownedY0, ownedY1);
+        lds = lds / (RT_BLOCK / 64) + 16;      // the light-candidate columns of one wave
     }
-    return hipGetLastError();
+    return with_flag(P.cacheWords != 0, [&](auto CACHED) { return with_flag(full, [&](auto FULL) {
+        constexpr int BLOCK = decltype(CACHED)::value ? RT_BLOCK : 64;
+        return launch(lean_frame_kernel<decltype(CACHED)::value, decltype(FULL)::value, LEAN_WAVES, BLOCK>, grid, BLOCK, lds, s, P, I, hitInstance, cur, ownedY0, ownedY1);
+    }); });
 }
 hipError_t RT_LAUNCHER(launch_indirect)(const FrameParams &P, const ViewImages &I, int cur, bool writeFiltered, bool klist, int walk, unsigned groups, int writeGuide, hipStream_t s) {
     RT_ROUTE_SIMPLE(launch_indirect_simple(P, I, cur, writeFiltered, klist, walk, groups, writeGuide, s));
-    const bool second = P.giBounces >= 2u;
-    if (klist && second) LAUNCH_RAY((indirect_kernel<true, true>), P, I, cur, writeFiltered ? 1 : 0);
-    if (klist) LAUNCH_RAY(indirect_kernel<true>, P, I, cur, writeFiltered ? 1 : 0);
-    if ((P.giSamples == 0 || !I.bounceRecords) && second) LAUNCH_RAY((indirect_kernel<false, true>), P, I, cur, writeFiltered ? 1 : 0);
-    if (P.giSamples == 0 || !I.bounceRecords) LAUNCH_RAY(indirect_kernel<false>, P, I, cur, writeFiltered ? 1 : 0);
+    const bool second = P.giBounces >= 2u, cached = P.cacheWords != 0;
+    if (klist || P.giSamples == 0 || !I.bounceRecords)          // the pass in one kernel
+        return with_flag(klist, [&](auto KLIST) { return with_flag(second, [&](auto SECOND) {
+            return launch(indirect_kernel<decltype(KLIST)::value, decltype(SECOND)::value>, rt_grid(P), RT_BLOCK, 0, s, P, I, cur, writeFiltered ? 1 : 0);
+        }); });
     // grid of the bounce kernels: one workgroup per tile up to `groups` workgroups (0 = RT_MAX_BOUNCE_GROUPS), then tiles b, b + grid, ... (bounce_tile_of)
     unsigned grid = rt_grid(P);
     {
@@ -1902,28 +1311,19 @@ hipError_t RT_LAUNCHER(launch_indirect)(const FrameParams &P, const ViewImages &
         const unsigned per = tiles > cap ? (tiles + cap - 1) / cap : 1u;
         if (walk != BOUNCE_WALK_REFILL) grid = tiles < 1u ? 1u : (tiles + per - 1) / per;
     }
-    if (walk == BOUNCE_WALK_REFILL) hipLaunchKernelGGL(bounce_trace_refill_kernel, dim3(grid), dim3(RT_BLOCK), 0, s, P, I);
-    else if (walk == BOUNCE_WALK_SPLIT && P.cacheWords) hipLaunchKernelGGL(bounce_trace_split_kernel<true>, dim3(grid), dim3(RT_BLOCK), cached_lds_bytes(P, false), s, P, I);
-    else if (walk == BOUNCE_WALK_SPLIT) hipLaunchKernelGGL(bounce_trace_split_kernel<false>, dim3(grid), dim3(RT_BLOCK), 0, s, P, I);
-    else if (P.cacheWords) hipLaunchKernelGGL(bounce_trace_plain_kernel<true>, dim3(grid), dim3(RT_BLOCK), cached_lds_bytes(P, false), s, P, I);
-    else hipLaunchKernelGGL(bounce_trace_plain_kernel<false>, dim3(grid), dim3(RT_BLOCK), 0, s, P, I);
+    // (enqueue: one hipGetLastError behind the chain reports the first launch that failed)
+    if (walk == BOUNCE_WALK_REFILL) enqueue(bounce_trace_refill_kernel, grid, RT_BLOCK, 0, s, P, I);
+    else with_flag(cached, [&](auto CACHED) {
+        if (walk == BOUNCE_WALK_SPLIT) enqueue(bounce_trace_split_kernel<decltype(CACHED)::value>, grid, RT_BLOCK, CACHED ? cached_lds_bytes(P, false) : 0, s, P, I);
+        else enqueue(bounce_trace_plain_kernel<decltype(CACHED)::value>, grid, RT_BLOCK, CACHED ? cached_lds_bytes(P, false) : 0, s, P, I);
+    });
     // same grid for the three kernels: workgroup b shades the segments workgroup b of bounce_trace filled (lengths stay on the device)
-    if (P.cacheWords && second) hipLaunchKernelGGL((bounce_hit_kernel<true, true>), dim3(grid), dim3(RT_BLOCK), cached_lds_bytes(P, true), s, P, I);
-    else if (second) hipLaunchKernelGGL((bounce_hit_kernel<false, true>), dim3(grid), dim3(RT_BLOCK), 0, s, P, I);
-    else if (P.cacheWords) hipLaunchKernelGGL(bounce_hit_kernel<true>, dim3(grid), dim3(RT_BLOCK), cached_lds_bytes(P, true), s, P, I);
-    else hipLaunchKernelGGL(bounce_hit_kernel<false>, dim3(grid), dim3(RT_BLOCK), 0, s, P, I);
-    if (walk == BOUNCE_WALK_REFILL) hipLaunchKernelGGL(bounce_miss_kernel, dim3(grid), dim3(RT_BLOCK), 0, s, P, I);      // the other walks finish their misses themselves
-    dim3 rgrid((unsigned)(P.width + 31) / 32, (unsigned)(P.tileY1 - P.tileY0 + 7) / 8);
-    hipLaunchKernelGGL(bounce_resolve_kernel, rgrid, dim3(256), 0, s, P, I, cur, writeFiltered ? 1 : 0, writeGuide);
-    return hipGetLastError();
+    with_flag(cached, [&](auto CACHED) { with_flag(second, [&](auto SECOND) {
+        enqueue(bounce_hit_kernel<decltype(CACHED)::value, decltype(SECOND)::value>, grid, RT_BLOCK, CACHED ? cached_lds_bytes(P, true) : 0, s, P, I);
+    }); });
+    if (walk == BOUNCE_WALK_REFILL) enqueue(bounce_miss_kernel, grid, RT_BLOCK, 0, s, P, I);      // the other walks finish their misses themselves
+    return launch(bounce_resolve_kernel, image_grid(P.width, P.tileY1 - P.tileY0), 256, 0, s, P, I, cur, writeFiltered ? 1 : 0, writeGuide);
 }
-#ifndef RT_ASSUME_SIMPLE
-hipError_t launch_indirect_constant(const FrameParams &P, const ViewImages &I, int cur, hipStream_t s) {
-    dim3 grid((unsigned)(P.width + 31) / 32, (unsigned)(P.tileY1 - P.tileY0 + 7) / 8);
-    hipLaunchKernelGGL(indirect_constant_kernel, grid, dim3(256), 0, s, P, I, cur);
-    return hipGetLastError();
-}
-#endif
 
 // Refraction / reflection only have work where the primary hit has the factor: most tiles return at once, so these two take one
 // workgroup per tile (up to 8192) and let the dispatcher balance them (C5 reflection: 0.315 -> 0.26 ms against the persistent grid).
@@ -1933,72 +1333,11 @@ static unsigned sparse_grid(const FrameParams &P) {
 }
 hipError_t RT_LAUNCHER(launch_refraction)(const FrameParams &P, const ViewImages &I, bool klist, hipStream_t s) {
     RT_ROUTE_SIMPLE(launch_refraction_simple(P, I, klist, s));
-    if (klist) hipLaunchKernelGGL(refraction_kernel<true>, dim3(sparse_grid(P)), dim3(RT_BLOCK), 0, s, P, I);
-    else hipLaunchKernelGGL(refraction_kernel<false>, dim3(sparse_grid(P)), dim3(RT_BLOCK), 0, s, P, I);
-    return hipGetLastError();
+    return with_flag(klist, [&](auto KLIST) { return launch(refraction_kernel<decltype(KLIST)::value>, sparse_grid(P), RT_BLOCK, 0, s, P, I); });
 }
 hipError_t RT_LAUNCHER(launch_reflection)(const FrameParams &P, const ViewImages &I, bool klist, int pass, bool last, int parity, hipStream_t s) {
     RT_ROUTE_SIMPLE(launch_reflection_simple(P, I, klist, pass, last, parity, s));
-    if (klist) hipLaunchKernelGGL(reflection_kernel<true>, dim3(sparse_grid(P)), dim3(RT_BLOCK), 0, s, P, I, pass, last ? 1 : 0, parity);
-    else if (P.cacheWords) hipLaunchKernelGGL((reflection_kernel<false, true>), dim3(sparse_grid(P)), dim3(RT_BLOCK), cached_lds_bytes(P, true), s, P, I, pass, last ? 1 : 0, parity);
-    else hipLaunchKernelGGL(reflection_kernel<false>, dim3(sparse_grid(P)), dim3(RT_BLOCK), 0, s, P, I, pass, last ? 1 : 0, parity);
-    return hipGetLastError();
+    if (klist) return launch(reflection_kernel<true>, sparse_grid(P), RT_BLOCK, 0, s, P, I, pass, last ? 1 : 0, parity);
+    if (P.cacheWords) return launch(reflection_kernel<false, true>, sparse_grid(P), RT_BLOCK, cached_lds_bytes(P, true), s, P, I, pass, last ? 1 : 0, parity);
+    return launch(reflection_kernel<false>, sparse_grid(P), RT_BLOCK, 0, s, P, I, pass, last ? 1 : 0, parity);
 }
-
-#ifndef RT_ASSUME_SIMPLE
-hipError_t launch_gaussian(const uint16_t *in, uint16_t *out, int width, int height, int y0, int y1, hipStream_t s) {
-    dim3 grid((unsigned)(width + 31) / 32, (unsigned)(y1 - y0 + 7) / 8);
-    hipLaunchKernelGGL(gaussian_kernel, grid, dim3(256), 0, s, in, out, width, height, y0, y1);
-    return hipGetLastError();
-}
-hipError_t launch_compose_post(const FrameParams &P, const ViewImages &I, int cur, bool lean, bool writeFinal, hipStream_t s) {
-    dim3 grid((unsigned)(P.width + 31) / 32, (unsigned)(P.tileY1 - P.tileY0 + 7) / 8);
-    if (lean) hipLaunchKernelGGL(compose_post_kernel<true>, grid, dim3(256), 0, s, P, I, cur, writeFinal ? 1 : 0);
-    else hipLaunchKernelGGL(compose_post_kernel<false>, grid, dim3(256), 0, s, P, I, cur, writeFinal ? 1 : 0);
-    return hipGetLastError();
-}
-hipError_t launch_tile_order(uint32_t *cost, uint32_t *order, uint32_t tiles, hipStream_t s) {
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, cost, order, tiles);
-    return hipGetLastError();
-}
-hipError_t launch_spp_accumulate(const FrameParams &P, const ViewImages &I, float *sum, int sub, int count, hipStream_t s) {
-    dim3 grid((unsigned)(P.width + 31) / 32, (unsigned)(P.tileY1 - P.tileY0 + 7) / 8);
-    hipLaunchKernelGGL(spp_accumulate_kernel, grid, dim3(256), 0, s, P, I, reinterpret_cast<float4 *>(sum), sub, count);
-    return hipGetLastError();
-}
-hipError_t launch_post_process(const FrameParams &P, const ViewImages &I, hipStream_t s) {
-    dim3 grid((unsigned)((int)P.resolution[2] + 31) / 32, (unsigned)((int)P.resolution[3] + 7) / 8);
-    hipLaunchKernelGGL(post_process_kernel, grid, dim3(256), 0, s, P, I);
-    return hipGetLastError();
-}
-hipError_t launch_debug_view(const FrameParams &P, const ViewImages &I, const DebugSource &src, hipStream_t s) {
-    dim3 grid((unsigned)((int)P.resolution[2] + 31) / 32, (unsigned)((int)P.resolution[3] + 7) / 8);
-    hipLaunchKernelGGL(debug_view_kernel, grid, dim3(256), 0, s, P, I, src);
-    return hipGetLastError();
-}
-__global__ __launch_bounds__(256) void stack_slab_init_kernel(uint32_t *slab, size_t lanes, const uint32_t *flag) {
-    const size_t lane = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (lane >= lanes) return;
-    const uint64_t p = reinterpret_cast<uint64_t>(flag);
-    uint32_t *h = slab + lane * (RT_STACK_SPILL_HEADER + RT_STACK_SPILL);
-    h[0] = (uint32_t)p; h[1] = (uint32_t)(p >> 32);
-}
-hipError_t launch_stack_slab_init(uint32_t *slab, size_t lanes, const uint32_t *flagDevicePointer, hipStream_t s) {
-    if (!lanes) return hipSuccess;
-    hipLaunchKernelGGL(stack_slab_init_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, slab, lanes, flagDevicePointer);
-    return hipGetLastError();
-}
-hipError_t launch_apply_reflection_state(const ViewImages &I, int width, int y0, int y1, uint32_t frameTag, hipStream_t s) {
-    if (y1 <= y0) return hipSuccess;
-    dim3 grid((unsigned)(width + 31) / 32, (unsigned)(y1 - y0 + 7) / 8);
-    hipLaunchKernelGGL(apply_reflection_state_kernel, grid, dim3(256), 0, s, I, width, y0, y1, frameTag);
-    return hipGetLastError();
-}
-hipError_t launch_clear_final(const FrameParams &P, const ViewImages &I, hipStream_t s) {
-    dim3 grid((unsigned)(P.width + 31) / 32, (unsigned)(P.tileY1 - P.tileY0 + 7) / 8);
-    if (P.separatePost) grid = dim3((unsigned)((int)P.resolution[2] + 31) / 32, (unsigned)((int)P.resolution[3] + 7) / 8);
-    hipLaunchKernelGGL(clear_final_kernel, grid, dim3(256), 0, s, P, I);
-    return hipGetLastError();
-}
-#endif
-

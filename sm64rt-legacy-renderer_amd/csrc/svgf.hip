@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void svgf_guide_kernel(const int32_t *instance
 }
 
 #define ATROUS_ROWS 1
-// ComposePS of one pixel (ComposePS.hlsl:18-37 + the PostProcessPS passthrough; compose_post_kernel<false> of passes.hip, the same operations through the same
+// ComposePS of one pixel (ComposePS.hlsl:18-37 + the PostProcessPS passthrough; compose_post_kernel<false> of image_passes.hip, the same operations through the same
 // helpers -- none of them contracted, whatever this file's pragma says) with the filtered GI value the last a-trous iteration has just rounded to RGBA16F:
 // on frames with the SVGF denoiser the last iteration composes its pixel itself (one launch and one pass over the filtered image less per frame).
 DEV void compose_pixel(const SvgfComposeFold &f, size_t i, uint2 filtered) {
@@ -168,7 +168,7 @@ DEV void compose_pixel(const SvgfComposeFold &f, size_t i, uint2 filtered) {
     }
     else result = xyz(d);
     float4 v = make_float4(result.x, result.y, result.z, 1.0f);
-    if (f.sppCount > 1) {       // spp_accumulate_kernel of passes.hip, folded in as well (same additions in the same order, one multiplication by 1.0f / count at the end)
+    if (f.sppCount > 1) {       // spp_accumulate_kernel of image_passes.hip, folded in as well (same additions in the same order, one multiplication by 1.0f / count at the end)
         float4 *sum = reinterpret_cast<float4 *>(f.sppSum);
         if (f.sppSub > 0) { const float4 a = sum[i]; v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w; }
         if (f.sppSub + 1 < f.sppCount) {
