@@ -101,6 +101,8 @@ enum { /* ref:70-86 */
     RT64_UPSCALER_MODE_AUTO = 0x0, RT64_UPSCALER_MODE_ULTRA_PERFORMANCE = 0x1, RT64_UPSCALER_MODE_PERFORMANCE = 0x2,
     RT64_UPSCALER_MODE_BALANCED = 0x3, RT64_UPSCALER_MODE_QUALITY = 0x4, RT64_UPSCALER_MODE_ULTRA_QUALITY = 0x5,
     RT64_UPSCALER_MODE_NATIVE = 0x6,
+    /* MI355X library: AUTO and FSR select the built-in temporal upscaler, and RT64_VIEW_DESC.upscalerSharpness > 0 adds its RCAS sharpening pass;
+       DLSS and XESS fall back to the bilinear resample, where the field does nothing. */
     /* RT64_TEXTURE_FORMAT_DDS accepts (DX10 dxgiFormat / legacy FourCC / legacy 32-bit RGB masks): BC1 (71, 72 / DXT1), BC2 (74, 75 / DXT2, DXT3),
        BC3 (77, 78 / DXT4, DXT5), BC4_UNORM (80 / ATI1, BC4U), BC5_UNORM (83 / ATI2, BC5U), BC7 (98, 99), R8G8B8A8 (28, 29 / R mask 0xff),
        B8G8R8A8 (87, 91 / masks 0xff0000, 0xff00, 0xff, 0xff000000), B8G8R8X8 (88, 93 / the same with A = 0).  Every format is decoded to RGBA8 once
@@ -223,6 +225,8 @@ typedef struct {                                     /* ref:172-182, 32 bytes */
     float resolutionScale, motionBlurStrength;
     unsigned int diSamples, giSamples, maxLights;
     unsigned char upscaler, upscalerMode;
+    /* Sharpening behind the upscaler (FSR2's range: 0 = none ... 1 = strongest; above 1 acts as 1).  Above 0 and with upscaler AUTO or FSR, an RCAS pass
+       sharpens the upscaled image before PostProcessPS reads it; 0, negative, NaN, or any other upscaler: no pass (MI355X library: DESIGN.md 4, rules S1-S7). */
     float upscalerSharpness;
     bool denoiserEnabled;
 } RT64_VIEW_DESC;
@@ -406,7 +410,10 @@ enum {
                                                    normal z (f16 bits) | valid << 16, depth (f32 bits), depth gradient (f32 bits) */
     RT64_IMAGE_FILTER_PING = 25,       /* [f32 x4] filter ping-pong image 0 (RGBA16F): after a frame, the input of the LAST pass (a-trous iteration 4,
                                                    rgb + variance; or Gaussian pass 4, rgb + the raw image's history in alpha) */
-    RT64_IMAGE_COUNT_ = 26
+    RT64_IMAGE_SHARPENED = 26,         /* [f32 x4] screen size, the whole frame, like RT64_IMAGE_UPSCALED: the RCAS pass's result, which PostProcessPS samples --
+                                                   sharpened colour + the upscaled image's alpha.  Only after a frame that sharpened (upscalerSharpness > 0 behind
+                                                   the built-in upscaler, visualization_mode 0); refused with an error message otherwise */
+    RT64_IMAGE_COUNT_ = 27
 };
 
 /* Arrays returned by RT64_ReadbackMeshAccel / RT64_ReadbackViewAccel. */

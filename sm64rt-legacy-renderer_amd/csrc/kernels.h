@@ -142,6 +142,9 @@ hipError_t launch_svgf_atrous(const ViewImages &I, int width, int height, int y0
 // Temporal upscaler stage (Upscaler::upscale, rt64_view.cpp:1584-1618): rtOutput + flow + masks + depth (render size rw x rh, jitter jx / jy)
 // and the previous upscaled image -> `out` (display size dw x dh, RGBA32F: colour + accumulated frame count).
 hipError_t launch_taa_upsample(const ViewImages &I, int cur, int rw, int rh, float jx, float jy, const float *prev, float *out, int dw, int dh, bool haveHistory, hipStream_t s);
+// RCAS sharpening of the upscaled image (RT64_VIEW_DESC.upscalerSharpness; rules S1-S7): `in` -> `out`, both display size RGBA32F, in != out;
+// k = 2^(2 min(sharpness, 1) - 2) of rule S1.  Alpha (the frame count) is copied.
+hipError_t launch_rcas_sharpen(const float *in, float *out, int dw, int dh, float k, hipStream_t s);
 
 // ---- gather.hip -----------------------------------------------------------------------------------------------------
 // Rank 0 of a multi-GPU gather: frame row y <- row gather_row_owner(y) of the owner's packed buffer (`own` for rank 0, bucket + r * slotBytes for rank r).

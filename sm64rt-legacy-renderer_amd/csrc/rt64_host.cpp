@@ -370,6 +370,10 @@ struct View {
     int upscaler = RT64_UPSCALER_OFF, upscalerMode = RT64_UPSCALER_MODE_AUTO; float upscalerSharpness = 0.0f;
     bool upscaleActive = false; int jitterPhases = 1; float pixelJitter[2] = { 0.0f, 0.0f };
     float *upscaled[2] = { nullptr, nullptr }; int upW = 0, upH = 0, upSwap = 0; bool upValid = false;
+    // RCAS pass behind the upscaler (rules S1-S7): its own screen-size RGBA32F image, held only while upscalerSharpness > 0 behind the built-in upscaler
+    float *sharpened = nullptr; int sharpW = 0, sharpH = 0; bool sharpValid = false;       // sharpValid: the last frame wrote it (RT64_IMAGE_SHARPENED)
+    bool sharpenActive() const { return upscaleActive && upscalerSharpness > 0.0f; }      // (false for a NaN)
+    void releaseSharpened() { if (sharpened) hipFree(sharpened); sharpened = nullptr; sharpW = sharpH = 0; sharpValid = false; }
     Texture *skyPlane = nullptr;
     DevArray<uint32_t> skyTiled; uint32_t skyTiledSerial = 0; uint32_t skyTiledLog2[2] = { 0, 0 };     // level 0 of the sky plane in 4 x 4 tiles (FrameParams::skyTiled)
     Mat4 view = mat_identity(), projection = mat_identity(), viewI = mat_identity(), projectionI = mat_identity(), viewProj = mat_identity(), prevViewI = mat_identity(), prevViewProj = mat_identity();
@@ -904,6 +908,7 @@ void View::releaseImages() {
     allocations.clear(); img = ViewImages(); bounceSamples = 0; leanFrame = false; fusedFrame = false; for (auto &fb : finalBuf) fb = nullptr;
     for (auto &u : upscaled) { if (u) hipFree(u); u = nullptr; }
     upW = upH = 0; upValid = false;
+    releaseSharpened();
 }
 
 void View::createImages(int w, int h, int screenW, int screenH) {       // View::createOutputBuffers, rt64_view.cpp:105-298 (same formats)
@@ -1172,6 +1177,13 @@ void View::update() {                          // View::update, rt64_view.cpp:10
             upW = dev->width; upH = dev->height; upValid = false;
         }
         if (!upscaleActive) upValid = false;
+        if (!sharpenActive()) { if (sharpened) releaseSharpened(); }
+        else if (sharpW != dev->width || sharpH != dev->height) {
+            releaseSharpened();
+            HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&sharpened), (size_t)dev->width * dev->height * 16));
+            sharpW = dev->width; sharpH = dev->height;
+        }
+        sharpValid = false;
     }
     usedTextures.clear();
     auto textureIndex = [&](Texture *t) -> int {
@@ -1788,6 +1800,12 @@ void View::render() {                          // View::render, rt64_view.cpp:11
             L(launch_taa_upsample(img, cur, imgW, imgH, pixelJitter[0], pixelJitter[1], upscaled[upSwap ^ 1], upscaled[upSwap], finalW, finalH, upValid, s));
             P.postSource = upscaled[upSwap]; P.postSourceW = finalW; P.postSourceH = finalH;
             upValid = true; upSwap ^= 1;
+            if (sharpened && debugMode == 0) {      // S7: RCAS of this frame's upscaled image into an image of its own, which PostProcessPS samples; the history never sees it
+                // S1: k = 2^(2 s - 2), s = min(upscalerSharpness, 1) -- FSR2's 2 - 2 s "stops"
+                const float k = (float)std::exp2(2.0 * std::min((double)upscalerSharpness, 1.0) - 2.0);
+                L(launch_rcas_sharpen(P.postSource, sharpened, finalW, finalH, k, s));
+                P.postSource = sharpened; sharpValid = true;
+            }
         }
         if (debugMode != 0 && subFrame == subFrames - 1) {
             // DebugPS in PostProcess's place (rt64_view.cpp:1628-1650), blended over the cleared buffer + background instances (those are already there around a viewport
@@ -2039,6 +2057,14 @@ static size_t readback(Device *dev, int image, void *dst, size_t dstBytes, bool 
         if (!v->upscaleActive || !v->upValid) throw std::runtime_error("RT64_ReadbackDevice: no upscaled image (no upscaler is active).");
         if (dstBytes < need) throw std::runtime_error("RT64_ReadbackDevice: destination buffer is too small.");
         HIP_CHECK(hipMemcpyAsync(dst, v->upscaled[v->upSwap ^ 1], need, toDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, dev->stream));
+        HIP_CHECK(hipStreamSynchronize(dev->stream));
+        return need;
+    }
+    if (image == RT64_IMAGE_SHARPENED) {         // the RCAS pass's result of the last frame (what PostProcessPS sampled): screen size, whole frame
+        const size_t need = (size_t)v->finalW * v->finalH * 16;
+        if (!v->sharpened || !v->sharpValid) throw std::runtime_error("RT64_ReadbackDevice: no sharpened image (the last frame ran no sharpening pass: it needs upscalerSharpness > 0 behind the built-in upscaler).");
+        if (dstBytes < need) throw std::runtime_error("RT64_ReadbackDevice: destination buffer is too small.");
+        HIP_CHECK(hipMemcpyAsync(dst, v->sharpened, need, toDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, dev->stream));
         HIP_CHECK(hipStreamSynchronize(dev->stream));
         return need;
     }
@@ -2326,7 +2352,8 @@ RT64_EXPORT void RT64_SetViewDescription(RT64_VIEW *viewPtr, RT64_VIEW_DESC view
     v->diSamples = viewDesc.diSamples; v->giSamples = viewDesc.giSamples; v->denoiserEnabled = viewDesc.denoiserEnabled;
     // upscaler / upscalerMode (rt64_view.cpp:2109-2163): AUTO prefers DLSS, then XeSS on Intel, then FSR; the vendor SDKs do not exist here, so AUTO and
     // FSR select the built-in temporal upscaler (upscale.hip) and DLSS / XeSS fall back to the bilinear resample like an uninitialised SDK does (:116,139-141).
-    // upscalerSharpness is accepted and has no effect (no sharpening pass).
+    // upscalerSharpness (-> params.sharpness, :1607; FSR2's sharpening pass, rt64_fsr.cpp:148-149): above 0 and behind the built-in upscaler, an RCAS pass
+    // sharpens the upscaled image before PostProcessPS reads it (rules S1-S7, upscale.hip); 0, negative, NaN or without that upscaler: no pass.
     v->upscaler = viewDesc.upscaler; v->upscalerMode = viewDesc.upscalerMode; v->upscalerSharpness = viewDesc.upscalerSharpness;
 }
 RT64_EXPORT void RT64_SetViewSkyPlane(RT64_VIEW *viewPtr, RT64_TEXTURE *texturePtr) { View *v = reinterpret_cast<View *>(viewPtr); if (v) v->skyPlane = reinterpret_cast<Texture *>(texturePtr); }

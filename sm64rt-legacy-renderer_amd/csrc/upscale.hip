@@ -1,4 +1,5 @@
-// upscale.hip -- the temporal upscaler stage: jittered temporal-accumulation upsample of rtOutput to the display size.
+// upscale.hip -- the temporal upscaler stage: jittered temporal-accumulation upsample of rtOutput to the display size, and the RCAS sharpening
+// pass behind it (rcas_sharpen_kernel, at the end of the file).
 //
 // Stands where the reference calls a vendor SDK through `Upscaler::upscale` (private/rt64_upscaler.h:25-48; call site
 // private/rt64_view.cpp:1584-1618: colour, flow, reactive mask, lock mask, depth, the frame's jitter in, rtOutputUpscaled out, which
@@ -69,11 +70,47 @@ __global__ __launch_bounds__(256) void taa_upsample_kernel(const float4 *__restr
     out[(size_t)y * (size_t)dw + (size_t)x] = make_float4(cr2 + a * (cr - cr2), cg2 + a * (cg - cg2), cb2 + a * (cb - cb2), fminf(N + 1.0f, 32.0f));
 }
 
+// RCAS ("robust contrast-adaptive sharpening", the sharpener of FSR 1 / FSR 2) behind the upscaler: RT64_VIEW_DESC.upscalerSharpness, which the reference hands
+// to the upscaler SDK (rt64_view.cpp:1607; rt64_fsr.cpp:148-149 turns it into FSR2's sharpening pass).  Rules S1-S7 in DESIGN.md 4, restated in
+// tests/sharpen_rule.py, which the GPU tests hold this kernel to bit for bit: float32 in exactly this order, IEEE divisions, no fmaf.
+// Same shape as taa_upsample_kernel: one thread per display pixel, 32 x 8 per workgroup; five float4 taps (the neighbours' overlap: L1 / L2 hits), one
+// 16-byte store: ~32 B of HBM traffic per display pixel.
+DEV float sat01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }                                          // S2: a NaN becomes 0
+DEV float rcas_lobe(float b, float d, float e, float f, float h) {                                        // S3
+    const float mn = fminf(fminf(b, d), fminf(f, h)), mx = fmaxf(fmaxf(b, d), fmaxf(f, h));
+    const float hitMin = mx == 0.0f ? 0.0f : fminf(mn, e) / (4.0f * mx);
+    const float hitMax = mn == 1.0f ? 0.0f : (1.0f - fmaxf(mx, e)) / (4.0f * mn - 4.0f);
+    return fmaxf(-hitMin, hitMax);
+}
+DEV float rcas_filter(float lobe, float b, float d, float e, float f, float h) {                          // S5
+    return sat01((lobe * (((b + d) + f) + h) + e) / (4.0f * lobe + 1.0f));
+}
+
+__global__ __launch_bounds__(256) void rcas_sharpen_kernel(const float4 *__restrict__ in, float4 *__restrict__ out, int dw, int dh, float k) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= dw || y >= dh) return;
+    const int xl = x > 0 ? x - 1 : 0, xr = x < dw - 1 ? x + 1 : dw - 1, yu = y > 0 ? y - 1 : 0, yd = y < dh - 1 ? y + 1 : dh - 1;      // S2: clamped to the image
+    const size_t row = (size_t)y * (size_t)dw;
+    const float4 pb = in[(size_t)yu * (size_t)dw + (size_t)x], pd = in[row + (size_t)xl], pe = in[row + (size_t)x], pf = in[row + (size_t)xr], ph = in[(size_t)yd * (size_t)dw + (size_t)x];
+    const float br = sat01(pb.x), bg = sat01(pb.y), bb = sat01(pb.z), dr = sat01(pd.x), dg = sat01(pd.y), db = sat01(pd.z);
+    const float er = sat01(pe.x), eg = sat01(pe.y), eb = sat01(pe.z), fr = sat01(pf.x), fg = sat01(pf.y), fb = sat01(pf.z);
+    const float hr = sat01(ph.x), hg = sat01(ph.y), hb = sat01(ph.z);
+    const float lobeMax = fmaxf(fmaxf(rcas_lobe(br, dr, er, fr, hr), rcas_lobe(bg, dg, eg, fg, hg)), rcas_lobe(bb, db, eb, fb, hb));
+    const float lobe = fmaxf(-0.1875f, fminf(lobeMax, 0.0f)) * k;                                         // S4
+    out[row + (size_t)x] = make_float4(rcas_filter(lobe, br, dr, er, fr, hr), rcas_filter(lobe, bg, dg, eg, fg, hg), rcas_filter(lobe, bb, db, eb, fb, hb), pe.w);
+}
+
 }  // namespace
 
 hipError_t launch_taa_upsample(const ViewImages &I, int cur, int rw, int rh, float jx, float jy, const float *prev, float *out, int dw, int dh, bool haveHistory, hipStream_t s) {
     dim3 grid((unsigned)(dw + 31) / 32, (unsigned)(dh + 7) / 8);
     hipLaunchKernelGGL(taa_upsample_kernel, grid, dim3(256), 0, s, reinterpret_cast<const float4 *>(I.output), reinterpret_cast<const uint32_t *>(I.flow), I.reactiveMask, I.lockMask,
                        I.depth[cur], rw, rh, jx, jy, reinterpret_cast<const float4 *>(prev), reinterpret_cast<float4 *>(out), dw, dh, haveHistory ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_rcas_sharpen(const float *in, float *out, int dw, int dh, float k, hipStream_t s) {
+    dim3 grid((unsigned)(dw + 31) / 32, (unsigned)(dh + 7) / 8);
+    hipLaunchKernelGGL(rcas_sharpen_kernel, grid, dim3(256), 0, s, reinterpret_cast<const float4 *>(in), reinterpret_cast<float4 *>(out), dw, dh, k);
     return hipGetLastError();
 }

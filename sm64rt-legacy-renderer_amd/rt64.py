@@ -29,7 +29,7 @@ ACCEL_NODES, ACCEL_TRIANGLES, ACCEL_SORTED_INDEX, ACCEL_MORTON, ACCEL_HEADER, AC
  IMAGE_INDIRECT_LIGHT_FILTERED, IMAGE_REFLECTION, IMAGE_REFRACTION, IMAGE_TRANSPARENT, IMAGE_FLOW,
  IMAGE_REACTIVE_MASK, IMAGE_LOCK_MASK, IMAGE_DEPTH, IMAGE_OUTPUT_RGBA32F, IMAGE_PRIMARY_HIT,
  IMAGE_VIEW_DIRECTION, IMAGE_FIRST_INSTANCE_ID, IMAGE_BACKGROUND, IMAGE_UPSCALED,
- IMAGE_GI_MOMENTS, IMAGE_FILTER_GUIDE, IMAGE_FILTER_PING) = range(26)
+ IMAGE_GI_MOMENTS, IMAGE_FILTER_GUIDE, IMAGE_FILTER_PING, IMAGE_SHARPENED) = range(27)
 
 # image id -> (numpy dtype string, channels)
 IMAGE_FORMATS = {
@@ -41,6 +41,7 @@ IMAGE_FORMATS = {
     IMAGE_DEPTH: ("f4", 1), IMAGE_OUTPUT_RGBA32F: ("f4", 4), IMAGE_PRIMARY_HIT: ("u4", 4),
     IMAGE_VIEW_DIRECTION: ("f4", 4), IMAGE_FIRST_INSTANCE_ID: ("i4", 1), IMAGE_BACKGROUND: ("u1", 4), IMAGE_UPSCALED: ("f4", 4),
     IMAGE_GI_MOMENTS: ("f4", 2), IMAGE_FILTER_GUIDE: ("u4", 4), IMAGE_FILTER_PING: ("f4", 4),
+    IMAGE_SHARPENED: ("f4", 4),
 }
 
 
