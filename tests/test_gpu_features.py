@@ -143,7 +143,8 @@ def test_soft_shadows_many_lights(rt64_lib, sample_data):
         d.lights = ls
     got, ref, st = _render_pair(rt64_lib, _variant(sample_data, mod), view_desc=dict(di_samples=2, max_lights=3))
     # light selection thresholds and disc-sample positions go through pow/rsqrt (1-ulp device ops): ray counts match,
-    # individual shadow rays may differ in the last bit, so node counts are compared loosely
+    # individual shadow rays may differ in the last bit, so node counts are compared loosely.  Which pixels float32 can legitimately decide the other way, and that
+    # every other one holds a derived bound, is shown by tests/test_gpu_light_rule.py.
     _check(got, ref, None)
     c = ref["counters"]
     assert st.shadowRays == c["shadowRays"] and abs(st.nodesVisited - c["nodesVisited"]) < 1e-3 * c["nodesVisited"]

@@ -158,6 +158,7 @@ def compare(got, ref, st, chosen):
     # Rays towards a light pick the light and its sample point through pow / rsqrt (1-ulp device operations, Lights.hlsli:115-168): with several lights a few
     # shadow rays differ in their last bits, so the visit counts agree to a few parts in 10^5 and a handful of pixels on a selection / shadow threshold differ outright
     # (seed 51, four lights inside a large sphere: 72 scattered pixels of 57 600, every one of them in the direct-light image only: tools/exp/r04_fuzz_detail.py).
+    # Which pixels float32 can legitimately decide the other way, and that every other one holds a derived bound, is shown by tests/test_gpu_light_rule.py.
     loose = chosen["lights"] > 1
     # ... and a mirror or refraction ray starts from the shading normal, a tolerance-level value: a few such rays in a million take another
     # path through the tree (seed 5039, three mirror / translucent spheres around the eye: 41 of 8.8 M visits, 7 pixels of 57 600 beyond 0.02)
