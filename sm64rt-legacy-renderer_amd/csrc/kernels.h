@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
-#include "../../include/rt64_query.h"
+#include "../../include/rt64_surface.h"      // (includes rt64_query.h)
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -106,6 +106,11 @@ hipError_t launch_spp_accumulate(const FrameParams &P, const ViewImages &I, floa
 // P.traversalStack: a slab of ray_query_spill_bytes() with its lane headers written, or nullptr when no walk of the scene outgrows the LDS stack.
 size_t ray_query_spill_bytes();
 hipError_t launch_ray_query(const FrameParams &P, const void *rays, void *hits, uint64_t count, uint32_t flags, hipStream_t s);
+
+// ---- surface.hip ---------------------------------------------------------------------------------------------------
+// RT64_ResolveViewRayHits: `count` RT64_RAYs and their RT64_RAY_HITs -> RT64_RAY_SURFACEs (device pointers, 16-byte aligned) from the instance table of P and the
+// vertex / index arrays it points to (rules A1-A9).  Reads neither P.traversalStack nor the LDS scene cache.
+hipError_t launch_hit_surface(const FrameParams &P, const void *rays, const void *hits, void *surfaces, uint64_t count, hipStream_t s);
 
 // ---- raster.hip ----------------------------------------------------------------------------------------------------
 size_t raster_tri_bytes(uint32_t triTotal);       // setup records of a draw list

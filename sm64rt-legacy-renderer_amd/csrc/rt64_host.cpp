@@ -225,8 +225,8 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits;
-    void awaitQueries();          // host-waits for every query still enqueued on a caller stream (before a BLAS it may read is rewritten or freed)
+    DevArray<uint8_t> queryRays, queryHits, querySurfaces;
+    void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
     uint8_t *finalOverride = nullptr;     // direct gather (RT64_SetGatherDirect): the back buffer of the frame in hand IS the gather's frame slot -- on rank 0 its own memory, on the others rank 0's through an IPC mapping (peer stores over xGMI)
@@ -753,7 +753,7 @@ void Mesh::set(const void *vertexArray, int vcount, int vstride, const unsigned 
     memcpy(hostBmin, mn, 12); memcpy(hostBmax, mx, 12);
     device->enter();
     if (vertices.ptr) device->beforeSceneMutation();       // a kept lean frame may still read this mesh's arrays (a first upload changes nothing a frame has seen)
-    if (vertices.ptr) device->awaitQueries();              // ... and so may a ray query on a caller stream (its BLAS is refitted in place or reallocated below)
+    if (vertices.ptr) device->awaitQueries();              // ... and so may a ray query or a resolve on a caller stream (the arrays are rewritten or reallocated below, the BLAS refitted in place or reallocated)
     // rt64_mesh.cpp:30-39,76-82: a change of counts/stride discards the BLAS even if updatable.
     const bool sameShape = vertices.ptr && vertexCount == vcount && vertexStride == vstride && indexCount == icount;
     // A build that is still only recorded has to run on the arrays it was recorded for when this call is going to REFIT its tree (the
@@ -2161,16 +2161,24 @@ static void query_overflow_check(Device *dev, const char *fn) {
                              std::to_string(RT_STACK_LDS + RT_STACK_SPILL) + " levels): their hits are missing geometry.");
 }
 
-// hostArrays: rays / hits in host memory, staged in chunks through pinned memory on the device's stream.  Otherwise device arrays, on `stream` (NULL: the device's stream).
-static void trace_view_rays(const char *fn, View *v, const void *rays, void *hits, size_t count, unsigned flags, void *stream, bool hostArrays) {
+// What one call does with its records: the walk (query.hip), the surface records of hits (surface.hip), or both back to back.
+enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2 };
+
+// hostArrays: rays / hits / surfaces in host memory, staged in chunks through pinned memory on the device's stream.  Otherwise device arrays, on `stream` (NULL: the device's stream).
+// work = QUERY_TRACE: rays -> hits (RT64_TraceViewRays).  QUERY_RESOLVE: rays + hits -> surfaces (RT64_ResolveViewRayHits).  Both: rays -> hits -> surfaces, host arrays only,
+// and `hits` may be NULL (RT64_TraceViewRaySurfaces).
+static void run_view_query(const char *fn, View *v, const void *rays, void *hits, void *surfaces, size_t count, unsigned flags, void *stream, bool hostArrays, int work) {
     auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool trace = (work & QUERY_TRACE) != 0, resolve = (work & QUERY_RESOLVE) != 0;
     if (!v) fail("NULL view.");
-    if (!rays || !hits) fail("NULL ray or hit array.");
+    if (!resolve) { if (!rays || !hits) fail("NULL ray or hit array."); }
+    else if (!rays || !surfaces || (!hits && !trace)) fail("NULL ray, hit or surface array.");
     if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RAY_FLAG_ACCEPT_FIRST_HIT)) fail("unknown flags.");
-    if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u)) fail("the ray and hit arrays must be 16-byte aligned.");
+    if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surfaces)) & 15u))
+        fail(resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
-    // Q7: the BLASes the frame traced must still be the ones it traced
+    // Q7 / A9: the BLASes the frame traced, and the vertex and index arrays they were built from, must still be the ones it traced
     if (!q.valid) fail("the view has no frame to query (draw one first).");
     if (q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
     for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
@@ -2182,7 +2190,7 @@ static void trace_view_rays(const char *fn, View *v, const void *rays, void *hit
     FrameParams P = q.P;
     P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
     P.tileTiming = nullptr; P.traversalStack = nullptr;
-    if (q.needSpill) {         // the walk can outgrow its LDS entries: the query's own slab, sized for its launch
+    if (trace && q.needSpill) {         // the walk can outgrow its LDS entries: the query's own slab, sized for its launch
         const size_t words = ray_query_spill_bytes() / sizeof(uint32_t);
         if (dev->querySlab.count < words) {
             dev->querySlab.reserve(words);
@@ -2195,23 +2203,37 @@ static void trace_view_rays(const char *fn, View *v, const void *rays, void *hit
     const hipStream_t s = (!hostArrays && stream) ? static_cast<hipStream_t>(stream) : dev->stream;
     if (s != dev->stream) { HIP_CHECK(hipEventRecord(dev->queryOrder, dev->stream)); HIP_CHECK(hipStreamWaitEvent(s, dev->queryOrder, 0)); }
     if (P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slab
+    FrameParams R = P; R.traversalStack = nullptr;                    // the resolve reads the instance table and what it points to: no stack, no slab
     if (hostArrays) {
-        const size_t chunk = std::min<size_t>(count, (size_t)1 << 20), bytes = chunk * sizeof(RT64_RAY);
-        dev->queryRays.reserve(bytes); dev->queryHits.reserve(bytes);
-        uint8_t *pin = static_cast<uint8_t *>(dev->staging(bytes, 1));
+        // One round trip per chunk: [rays | hits] up as far as the call brings them, the kernels back to back, [hits | surfaces] down as far as the call wants them.
+        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE);
+        const size_t upB = rayB + (trace ? 0 : hitB), downB = ((trace && hits) ? hitB : 0) + (resolve ? surfB : 0);
+        const size_t chunk = std::min<size_t>(count, (size_t)1 << (resolve ? 18 : 20));
+        dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB);
+        if (resolve) dev->querySurfaces.reserve(chunk * surfB);
+        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
         for (size_t at = 0; at < count; at += chunk) {
             const size_t n = std::min(chunk, count - at);
-            memcpy(pin, static_cast<const uint8_t *>(rays) + at * sizeof(RT64_RAY), n * sizeof(RT64_RAY));
-            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, pin, n * sizeof(RT64_RAY), hipMemcpyHostToDevice, s));
-            HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
-            HIP_CHECK(hipMemcpyAsync(pin, dev->queryHits.ptr, n * sizeof(RT64_RAY_HIT), hipMemcpyDeviceToHost, s));
+            memcpy(pin, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
+            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, pin, n * rayB, hipMemcpyHostToDevice, s));
+            if (!trace) {
+                memcpy(pin + n * rayB, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, pin + n * rayB, n * hitB, hipMemcpyHostToDevice, s));
+            }
+            if (trace) HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
+            if (resolve) HIP_CHECK(launch_hit_surface(R, dev->queryRays.ptr, dev->queryHits.ptr, dev->querySurfaces.ptr, n, s));
+            uint8_t *down = pin;
+            if (trace && hits) { HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
+            if (resolve) HIP_CHECK(hipMemcpyAsync(down, dev->querySurfaces.ptr, n * surfB, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
-            memcpy(static_cast<uint8_t *>(hits) + at * sizeof(RT64_RAY_HIT), pin, n * sizeof(RT64_RAY_HIT));
+            if (trace && hits) memcpy(static_cast<uint8_t *>(hits) + at * hitB, pin, n * hitB);
+            if (resolve) memcpy(static_cast<uint8_t *>(surfaces) + at * surfB, down, n * surfB);
         }
     }
-    else HIP_CHECK(launch_ray_query(P, rays, hits, count, flags, s));
+    else if (trace) HIP_CHECK(launch_ray_query(P, rays, hits, count, flags, s));
+    else HIP_CHECK(launch_hit_surface(R, rays, hits, surfaces, count, s));
     if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
-    if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes) stay as they are until the query has run
+    if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes and the vertex / index arrays) stay as they are until the query has run
         hipEvent_t done = nullptr;
         HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
         const hipError_t e = hipEventRecord(done, s);
@@ -2375,10 +2397,20 @@ RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstanceAt(RT64_VIEW *viewPtr, i
 }
 // ---- ray queries (include/rt64_query.h) ----
 RT64_EXPORT int RT64_TraceViewRays(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, size_t count, unsigned int flags) {
-    RT64_TRY trace_view_rays("RT64_TraceViewRays", reinterpret_cast<View *>(view), rays, hits, count, flags, nullptr, true); return 1; RT64_CATCH(0)
+    RT64_TRY run_view_query("RT64_TraceViewRays", reinterpret_cast<View *>(view), rays, hits, nullptr, count, flags, nullptr, true, QUERY_TRACE); return 1; RT64_CATCH(0)
 }
 RT64_EXPORT int RT64_TraceViewRaysDevice(RT64_VIEW *view, const void *rays, void *hits, size_t count, unsigned int flags, void *stream) {
-    RT64_TRY trace_view_rays("RT64_TraceViewRaysDevice", reinterpret_cast<View *>(view), rays, hits, count, flags, stream, false); return 1; RT64_CATCH(0)
+    RT64_TRY run_view_query("RT64_TraceViewRaysDevice", reinterpret_cast<View *>(view), rays, hits, nullptr, count, flags, stream, false, QUERY_TRACE); return 1; RT64_CATCH(0)
+}
+// include/rt64_surface.h (rules A1-A9): the const casts only fit the shared signature, a resolve writes neither rays nor hits
+RT64_EXPORT int RT64_ResolveViewRayHits(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, RT64_RAY_SURFACE *surfaces, size_t count) {
+    RT64_TRY run_view_query("RT64_ResolveViewRayHits", reinterpret_cast<View *>(view), rays, const_cast<RT64_RAY_HIT *>(hits), surfaces, count, 0, nullptr, true, QUERY_RESOLVE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_ResolveViewRayHitsDevice(RT64_VIEW *view, const void *rays, const void *hits, void *surfaces, size_t count, void *stream) {
+    RT64_TRY run_view_query("RT64_ResolveViewRayHitsDevice", reinterpret_cast<View *>(view), rays, const_cast<void *>(hits), surfaces, count, 0, stream, false, QUERY_RESOLVE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRaySurfaces(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, RT64_RAY_SURFACE *surfaces, size_t count, unsigned int flags) {
+    RT64_TRY run_view_query("RT64_TraceViewRaySurfaces", reinterpret_cast<View *>(view), rays, hits, surfaces, count, flags, nullptr, true, QUERY_TRACE | QUERY_RESOLVE); return 1; RT64_CATCH(0)
 }
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {
     const View *v = reinterpret_cast<View *>(viewPtr);

@@ -228,6 +228,13 @@ QUERY_API = [
     ("GetViewRaytracedInstance", "RT64_GetViewRaytracedInstance", _P, [_P, C.c_int]),
 ]
 RAY_FLAG_CULL_BACK_FACING, RAY_FLAG_ACCEPT_FIRST_HIT = 0x1, 0x2
+# include/rt64_surface.h: surface records for hits, again a list and a loader (RT64_LoadLibrarySurface) of its own
+SURFACE_API = [
+    ("ResolveViewRayHits", "RT64_ResolveViewRayHits", C.c_int, [_P, _P, _P, _P, C.c_size_t]),
+    ("ResolveViewRayHitsDevice", "RT64_ResolveViewRayHitsDevice", C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewRaySurfaces", "RT64_TraceViewRaySurfaces", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+SURFACE_VALID, SURFACE_BACK_FACE, SURFACE_HAS_UV, SURFACE_BAD_HIT = 0x1, 0x2, 0x4, 0x8
 
 
 class RAY(C.Structure):
@@ -239,7 +246,12 @@ class RAY_HIT(C.Structure):
                 ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint), ("reserved", C.c_uint)]
 
 
-assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32
+class RAY_SURFACE(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("flags", C.c_uint), ("geometricNormal", C.c_float * 3), ("instance", C.c_int),
+                ("shadingNormal", C.c_float * 3), ("primitive", C.c_uint), ("uv", C.c_float * 2), ("t", C.c_float), ("reserved", C.c_uint)]
+
+
+assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64
 
 HALO_ROWS = 62
 HALO_BYTES_PER_PIXEL = 24
@@ -264,7 +276,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -306,3 +318,44 @@ def trace_rays(lib, view, rays, flags=0, stream=None):
     if not ok:
         raise RuntimeError(lib.last_error())
     return hits
+
+
+def resolve_hits(lib, view, rays, hits, stream=None):
+    """RT64_ResolveViewRayHits: (N, 8) float32 rays and the (N, 8) float32 hits trace_rays returned for them -> (N, 16) float32 RT64_RAY_SURFACEs:
+    position xyz, flags, geometricNormal xyz, instance, shadingNormal xyz, primitive, uv, t, reserved (flags, instance, primitive as uint32 / int32
+    bits: read them through `.view(int32)`).  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    if type(rays).__module__.split(".")[0] == "torch":
+        import torch
+        for a in (rays, hits):
+            if a.dim() != 2 or a.shape[1] != 8 or a.dtype != torch.float32 or not a.is_cuda:
+                raise ValueError("rays, hits: (N, 8) float32 CUDA tensors")
+        if rays.shape[0] != hits.shape[0]:
+            raise ValueError("one hit per ray")
+        rays, hits = rays.contiguous(), hits.contiguous()
+        out = torch.empty((rays.shape[0], 16), dtype=torch.float32, device=rays.device)
+        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+        if s != torch.cuda.current_stream(rays.device):
+            rays.record_stream(s); hits.record_stream(s); out.record_stream(s)
+        ok = lib.ResolveViewRayHitsDevice(view, rays.data_ptr(), hits.data_ptr(), out.data_ptr(), rays.shape[0], s.cuda_stream)
+    else:
+        import numpy as np
+        rays, hits = np.ascontiguousarray(rays, dtype=np.float32), np.ascontiguousarray(hits, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != rays.shape:
+            raise ValueError("rays, hits: (N, 8) float32 arrays of one length")
+        out = np.empty((rays.shape[0], 16), dtype=np.float32)
+        ok = lib.ResolveViewRayHits(view, rays.ctypes.data, hits.ctypes.data, out.ctypes.data, rays.shape[0])
+    if not ok:
+        raise RuntimeError(lib.last_error())
+    return out
+
+
+def trace_surfaces(lib, view, rays, flags=0):
+    """RT64_TraceViewRaySurfaces on an (N, 8) float32 NumPy array of rays: trace and resolve in one staging round trip -> (hits (N, 8), surfaces (N, 16))."""
+    import numpy as np
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("rays: an (N, 8) float32 array")
+    hits, out = np.empty_like(rays), np.empty((rays.shape[0], 16), dtype=np.float32)
+    if not lib.TraceViewRaySurfaces(view, rays.ctypes.data, hits.ctypes.data, out.ctypes.data, rays.shape[0], flags):
+        raise RuntimeError(lib.last_error())
+    return hits, out
