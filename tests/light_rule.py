@@ -240,30 +240,37 @@ class BruteForceShadows:
 
     @staticmethod
     def _chunk(v0, e1, e2, o, d, tmin, tmax, tmin_e, tmax_e):
-        l1, l2, l0 = np.linalg.norm(e1, axis=1), np.linalg.norm(e2, axis=1), np.linalg.norm(v0, axis=1)
-        e1, e2 = e1[None], e2[None]
-        p = np.cross(d[:, None, :], e2)
-        det = np.einsum("ntk,ntk->nt", np.broadcast_to(e1, p.shape), p)
-        tv = o[:, None, :] - v0[None]
-        q = np.cross(tv, e1)
-        T = np.linalg.norm(tv, axis=2) + (np.linalg.norm(o, axis=1)[:, None] + l0[None]) / SHADOW_K
-        dl = np.linalg.norm(d, axis=1)[:, None]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = 1.0 / det
-            u = np.einsum("ntk,ntk->nt", tv, p) * inv
-            v = np.einsum("nk,ntk->nt", d, q) * inv
-            t = np.einsum("ntk,ntk->nt", np.broadcast_to(e2, q.shape), q) * inv
-            k = SHADOW_K * U
-            du = k * (T * dl * l2[None] * np.abs(inv) + np.abs(u))
-            dv = k * (T * dl * l1[None] * np.abs(inv) + np.abs(v))
-            dt = k * (T * l1[None] * l2[None] * np.abs(inv) + np.abs(t))
+        u, v, t, du, dv, dt, _, ok = triangle_test(v0, e1, e2, o, d)
         w = 1.0 - u - v
         lo, hi = tmin[:, None], tmax[:, None]
         lo_e, hi_e = tmin_e[:, None] + dt, tmax_e[:, None] + dt
-        ok = np.isfinite(u) & np.isfinite(v) & np.isfinite(t) & np.isfinite(du) & np.isfinite(dv) & np.isfinite(dt)
         hit = ok & (u > du) & (v > dv) & (w > du + dv) & (t > lo + lo_e) & (t < hi - hi_e)
         miss = ok & ((u < -du) | (v < -dv) | (w < -(du + dv)) | (t < lo - lo_e) | (t > hi + hi_e))
         return hit.any(axis=1), miss.all(axis=1)
+
+
+def triangle_test(v0, e1, e2, o, d):
+    """Every ray (o, d: (N, 3)) against every triangle (v0, e1, e2: (T, 3)) in float64, with the margins of BruteForceShadows' docstring: returns
+    (u, v, t, d_u, d_v, d_t, det, ok), each (N, T); ok is False where a quantity is not finite (a ray in the triangle's plane)."""
+    l1, l2, l0 = np.linalg.norm(e1, axis=1), np.linalg.norm(e2, axis=1), np.linalg.norm(v0, axis=1)
+    e1, e2 = e1[None], e2[None]
+    p = np.cross(d[:, None, :], e2)
+    det = np.einsum("ntk,ntk->nt", np.broadcast_to(e1, p.shape), p)
+    tv = o[:, None, :] - v0[None]
+    q = np.cross(tv, e1)
+    T = np.linalg.norm(tv, axis=2) + (np.linalg.norm(o, axis=1)[:, None] + l0[None]) / SHADOW_K
+    dl = np.linalg.norm(d, axis=1)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / det
+        u = np.einsum("ntk,ntk->nt", tv, p) * inv
+        v = np.einsum("nk,ntk->nt", d, q) * inv
+        t = np.einsum("ntk,ntk->nt", np.broadcast_to(e2, q.shape), q) * inv
+        k = SHADOW_K * U
+        du = k * (T * dl * l2[None] * np.abs(inv) + np.abs(u))
+        dv = k * (T * dl * l1[None] * np.abs(inv) + np.abs(v))
+        dt = k * (T * l1[None] * l2[None] * np.abs(inv) + np.abs(t))
+    ok = np.isfinite(u) & np.isfinite(v) & np.isfinite(t) & np.isfinite(du) & np.isfinite(dv) & np.isfinite(dt)
+    return u, v, t, du, dv, dt, det, ok
 
 
 # ---- the light loop ------------------------------------------------------------------------------------------------------------------------
@@ -330,7 +337,7 @@ def _compute_light(L, st, active, mutate):                                      
         tmin = add(RAY_MIN_DISTANCE, st["shadowRayBias"]) if mutate != "tmin_no_bias" else F(np.full(n, RAY_MIN_DISTANCE))
         tmax = sub(sample_dist, L["shadowOffset"]) if mutate != "offset_added" else add(sample_dist, L["shadowOffset"])
         sh = np.ones(n, dtype=np.int8)
-        if active.any():
+        if active.any() and st.get("checkShadows", True):
             o = np.stack([c.v for c in position], axis=-1)[active]
             d = np.stack([c.v for c in sample_dir], axis=-1)[active]
             sh[active] = st["shadow"](o, d, tmin.v[active], tmax.v[active], tmin.e[active], tmax.e[active])
@@ -346,29 +353,14 @@ def _compute_light(L, st, active, mutate):                                      
     return out, undecided, shadowed
 
 
-def direct_light(position, normal, specular, instance_id, materials, lights, eye_diffuse, eye_specular, max_lights, di_samples, frame_count, bluenoise, camera,
-                 shadow, mutate=None):
-    """resDirect of DirectRayGen for every pixel of a frame, as the RGBA16F image stores it when nothing is accumulated (w = 1; a miss is (1, 1, 1, 0), D:18-21).
+def light_loop(st, mask_bits, lights, max_lights, mutate=None):
+    """compute_lights_random (L:115-168) for n points: the candidate scan, `max_lights` draws by the CDF walk, each drawn light through _compute_light.
 
-    position, normal, specular: (H, W, >= 3) as stored (float32 / f16 values); instance_id: (H, W) int, < 0 for a miss; materials: per instance id a dict of the fields
-    the loop reads (lightGroupMaskBits, ignoreNormalFactor, specularExponent, shadowRayBias, selfLight); lights: dicts of the RT64_LIGHT fields; camera: dict(view, fov,
-    near, far, width, height, jitter); shadow: see BruteForceShadows.  Returns (value (H, W, 4), bound (H, W, 4), decided (H, W), info): |stored - value| <= bound is
-    claimed for every decided pixel; info holds per-pixel facts about the rule's own evaluation (in shadow, lights drawn, candidates admitted, number of lights its mask lets through whose radius it lies beyond)."""
-    assert mutate is None or mutate in MUTATIONS, mutate
-    h, w = instance_id.shape
-    lit = instance_id >= 0
-    py, px = np.nonzero(lit)
-    n = len(px)
-    ids = instance_id[lit]
-    mat = {k: np.asarray([m[k] for m in materials], dtype=np.float64)[ids] for k in ("ignoreNormalFactor", "specularExponent", "shadowRayBias")}
-    mask_bits = np.asarray([m["lightGroupMaskBits"] for m in materials], dtype=np.uint32)[ids]
-    self_light = np.asarray([m["selfLight"] for m in materials], dtype=np.float64)[ids]
-    rd = ray_direction(camera, normalised=(mutate == "raydir_normalised"))[lit]
-    rd_err = CAM_K * U * np.abs(rd).max(axis=-1)
-    st = {"position": vec(np.asarray(position, dtype=np.float64)[lit]), "normal": vec(np.asarray(normal, dtype=np.float64)[lit]),
-          "specular": vec(np.asarray(specular, dtype=np.float64)[lit]), "rayDirection": [F(rd[:, c], rd_err) for c in range(3)],
-          "px": px, "py": py, "bluenoise": bluenoise, "frameCount": int(frame_count), "diSamples": int(di_samples), "shadow": shadow,
-          "ignoreNormalFactor": mat["ignoreNormalFactor"], "specularExponent": mat["specularExponent"], "shadowRayBias": mat["shadowRayBias"]}
+    st: position, normal, specular, rayDirection as three F of n values each (they may carry an error of their own); px, py (n,) int; bluenoise; frameCount;
+    diSamples; ignoreNormalFactor, specularExponent, shadowRayBias (n,) float64; shadow (see BruteForceShadows); checkShadows (default True: False sends no
+    shadow ray and every sample counts as clear).  mask_bits: (n,) uint32, the material's lightGroupMaskBits.
+    Returns (result: three F, why: the undecided pixels by kind of decision, candidates admitted, draws made, lights whose radius the point lies beyond, in shadow)."""
+    n = len(mask_bits)
     T = _light_table(lights)
     why = {k: np.zeros(n, dtype=bool) for k in ("admission", "walk", "shadow", "bound")}          # which kind of decision float32 could take the other way
     outside = np.zeros(n, dtype=np.int64)             # lights let through by the mask whose radius the pixel lies beyond
@@ -405,8 +397,8 @@ def direct_light(position, normal, specular, instance_id, materials, lights, eye
     in_shadow = np.zeros(n, dtype=bool)
     for s in range(int(draws.max()) if n else 0):
         active = s < draws
-        slot = frame_count + s + (1 if mutate == "select_slot_plus_one" else 0)
-        r = mul(blue_noise(bluenoise, px, py, slot, 0, mutate != "bn_no_xmod"), remaining)                   # (L:147)
+        slot = st["frameCount"] + s + (1 if mutate == "select_slot_plus_one" else 0)
+        r = mul(blue_noise(st["bluenoise"], st["px"], st["py"], slot, 0, mutate != "bn_no_xmod"), remaining)                   # (L:147)
         chosen = np.zeros(n, dtype=np.int64)
         running = s_int[0]
         walking = active.copy()
@@ -432,6 +424,34 @@ def direct_light(position, normal, specular, instance_id, materials, lights, eye
         why["shadow"] |= und
         in_shadow |= shd
         result = [where(active, add(a, mul(c, inv_p)), a) for a, c in zip(result, light)]                     # (L:163)
+
+    return result, why, count, draws, outside, in_shadow
+
+
+def direct_light(position, normal, specular, instance_id, materials, lights, eye_diffuse, eye_specular, max_lights, di_samples, frame_count, bluenoise, camera,
+                 shadow, mutate=None):
+    """resDirect of DirectRayGen for every pixel of a frame, as the RGBA16F image stores it when nothing is accumulated (w = 1; a miss is (1, 1, 1, 0), D:18-21).
+
+    position, normal, specular: (H, W, >= 3) as stored (float32 / f16 values); instance_id: (H, W) int, < 0 for a miss; materials: per instance id a dict of the fields
+    the loop reads (lightGroupMaskBits, ignoreNormalFactor, specularExponent, shadowRayBias, selfLight); lights: dicts of the RT64_LIGHT fields; camera: dict(view, fov,
+    near, far, width, height, jitter); shadow: see BruteForceShadows.  Returns (value (H, W, 4), bound (H, W, 4), decided (H, W), info): |stored - value| <= bound is
+    claimed for every decided pixel; info holds per-pixel facts about the rule's own evaluation (in shadow, lights drawn, candidates admitted, number of lights its mask lets through whose radius it lies beyond)."""
+    assert mutate is None or mutate in MUTATIONS, mutate
+    h, w = instance_id.shape
+    lit = instance_id >= 0
+    py, px = np.nonzero(lit)
+    n = len(px)
+    ids = instance_id[lit]
+    mat = {k: np.asarray([m[k] for m in materials], dtype=np.float64)[ids] for k in ("ignoreNormalFactor", "specularExponent", "shadowRayBias")}
+    mask_bits = np.asarray([m["lightGroupMaskBits"] for m in materials], dtype=np.uint32)[ids]
+    self_light = np.asarray([m["selfLight"] for m in materials], dtype=np.float64)[ids]
+    rd = ray_direction(camera, normalised=(mutate == "raydir_normalised"))[lit]
+    rd_err = CAM_K * U * np.abs(rd).max(axis=-1)
+    st = {"position": vec(np.asarray(position, dtype=np.float64)[lit]), "normal": vec(np.asarray(normal, dtype=np.float64)[lit]),
+          "specular": vec(np.asarray(specular, dtype=np.float64)[lit]), "rayDirection": [F(rd[:, c], rd_err) for c in range(3)],
+          "px": px, "py": py, "bluenoise": bluenoise, "frameCount": int(frame_count), "diSamples": int(di_samples), "shadow": shadow,
+          "ignoreNormalFactor": mat["ignoreNormalFactor"], "specularExponent": mat["specularExponent"], "shadowRayBias": mat["shadowRayBias"]}
+    result, why, count, draws, outside, in_shadow = light_loop(st, mask_bits, lights, max_lights, mutate=mutate)
 
     result = [add(a, F(self_light[:, c])) for c, a in enumerate(result)]        # (D:51)
     normal, ray_dir, spec = st["normal"], st["rayDirection"], st["specular"]
