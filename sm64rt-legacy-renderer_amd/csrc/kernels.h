@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
-#include "../../include/rt64_surface.h"      // (includes rt64_query.h)
+#include "../../include/rt64_material.h"     // (includes rt64_surface.h and rt64_query.h)
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -111,6 +111,11 @@ hipError_t launch_ray_query(const FrameParams &P, const void *rays, void *hits, 
 // RT64_ResolveViewRayHits: `count` RT64_RAYs and their RT64_RAY_HITs -> RT64_RAY_SURFACEs (device pointers, 16-byte aligned) from the instance table of P and the
 // vertex / index arrays it points to (rules A1-A9).  Reads neither P.traversalStack nor the LDS scene cache.
 hipError_t launch_hit_surface(const FrameParams &P, const void *rays, const void *hits, void *surfaces, uint64_t count, hipStream_t s);
+
+// ---- material.hip --------------------------------------------------------------------------------------------------
+// RT64_ShadeViewRayHits: `count` RT64_RAYs, their RT64_RAY_HITs and (lods != nullptr) one float lod per record -> RT64_RAY_MATERIALs (device pointers, 16-byte aligned;
+// lods 4) from the instance and texture tables of P and the vertex, index and texel arrays they point to (rules H1-H12).  Reads neither P.traversalStack nor the LDS scene cache.
+hipError_t launch_hit_material(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *materials, uint64_t count, hipStream_t s);
 
 // ---- raster.hip ----------------------------------------------------------------------------------------------------
 size_t raster_tri_bytes(uint32_t triTotal);       // setup records of a draw list

@@ -225,7 +225,7 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits, querySurfaces;
+    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials;
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -448,10 +448,12 @@ struct View {
     struct QueryScene {
         bool valid = false;                       // a frame was drawn (a refused frame clears it: View::discardUpdate)
         bool meshDestroyed = false;               // RT64_DestroyMesh on a mesh that frame traced
+        bool textureDestroyed = false;            // RT64_DestroyTexture on a texture that frame's table holds (material records only: H11)
         FrameParams P;                            // instances, TLAS, LDS scene-cache image of the frame's table slot
         int slot = 0; bool needSpill = false;
         std::vector<std::pair<Mesh *, uint32_t>> meshes;      // the meshes the frame traced and the version (RT64_SetMesh count) it traced
         std::vector<Instance *> instances;                    // TLAS build position -> handle
+        std::vector<std::pair<Texture *, uint32_t>> textures;     // the textures of the frame's table and their serials (an address alone does not identify a texture)
     } query;
     void snapshotQueryScene();
     void pruneQueryEvents(bool wait);             // forget the completed query events of every slot (wait: host-wait for the others first)
@@ -2134,9 +2136,14 @@ static size_t readback(Device *dev, int image, void *dst, size_t dstBytes, bool 
 
 // The tables of the frame just drawn: what queries walk until the next frame.
 void View::snapshotQueryScene() {
-    query.valid = true; query.meshDestroyed = false; query.slot = tabCur; query.needSpill = needSpillSlab;
-    query.meshes.clear(); query.instances.clear();
-    for (const RenderInstance &ri : rtInstances) { query.meshes.emplace_back(ri.instance->mesh, ri.instance->mesh->version); query.instances.push_back(ri.instance); }
+    query.valid = true; query.meshDestroyed = false; query.textureDestroyed = false; query.slot = tabCur; query.needSpill = needSpillSlab;
+    query.meshes.clear(); query.instances.clear(); query.textures.clear();
+    auto holds = [&](Texture *t) { if (t && (query.textures.empty() || query.textures.back().first != t)) query.textures.emplace_back(t, t->serial); };
+    for (const RenderInstance &ri : rtInstances) {
+        query.meshes.emplace_back(ri.instance->mesh, ri.instance->mesh->version); query.instances.push_back(ri.instance);
+        holds(ri.instance->diffuse); holds(ri.instance->normal); holds(ri.instance->specular);      // what hit_material_kernel can reach through the instance table
+    }
+    std::sort(query.textures.begin(), query.textures.end()); query.textures.erase(std::unique(query.textures.begin(), query.textures.end()), query.textures.end());
     if (!rtInstances.empty()) query.P = lastParams;          // (View::render keeps the parameters of a frame with ray-traced instances)
     else memset(&query.P, 0, sizeof(query.P));                // instanceCount 0: every ray misses
 }
@@ -2162,26 +2169,29 @@ static void query_overflow_check(Device *dev, const char *fn) {
 }
 
 // What one call does with its records: the walk (query.hip), the surface records of hits (surface.hip), or both back to back.
-enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2 };
+enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2, QUERY_SHADE = 4 };
 
 // hostArrays: rays / hits / surfaces in host memory, staged in chunks through pinned memory on the device's stream.  Otherwise device arrays, on `stream` (NULL: the device's stream).
 // work = QUERY_TRACE: rays -> hits (RT64_TraceViewRays).  QUERY_RESOLVE: rays + hits -> surfaces (RT64_ResolveViewRayHits).  Both: rays -> hits -> surfaces, host arrays only,
-// and `hits` may be NULL (RT64_TraceViewRaySurfaces).
-static void run_view_query(const char *fn, View *v, const void *rays, void *hits, void *surfaces, size_t count, unsigned flags, void *stream, bool hostArrays, int work) {
+// and `hits` may be NULL (RT64_TraceViewRaySurfaces).  QUERY_SHADE in place of QUERY_RESOLVE: `surfaces` holds RT64_RAY_MATERIALs and `lods` (or NULL) travels with the rays
+// (RT64_ShadeViewRayHits, RT64_TraceViewRayMaterials; material.hip).
+static void run_view_query(const char *fn, View *v, const void *rays, void *hits, void *surfaces, size_t count, unsigned flags, void *stream, bool hostArrays, int work, const void *lods = nullptr) {
     auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
-    const bool trace = (work & QUERY_TRACE) != 0, resolve = (work & QUERY_RESOLVE) != 0;
+    const bool trace = (work & QUERY_TRACE) != 0, shade = (work & QUERY_SHADE) != 0, resolve = (work & (QUERY_RESOLVE | QUERY_SHADE)) != 0;
     if (!v) fail("NULL view.");
     if (!resolve) { if (!rays || !hits) fail("NULL ray or hit array."); }
-    else if (!rays || !surfaces || (!hits && !trace)) fail("NULL ray, hit or surface array.");
+    else if (!rays || !surfaces || (!hits && !trace)) fail(shade ? "NULL ray, hit or material array." : "NULL ray, hit or surface array.");
     if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RAY_FLAG_ACCEPT_FIRST_HIT)) fail("unknown flags.");
     if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surfaces)) & 15u))
-        fail(resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
+        fail(shade ? "the ray, hit and material arrays must be 16-byte aligned." : resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
+    if (!hostArrays && (reinterpret_cast<uintptr_t>(lods) & 3u)) fail("the lod array must be 4-byte aligned.");
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
     // Q7 / A9: the BLASes the frame traced, and the vertex and index arrays they were built from, must still be the ones it traced
     if (!q.valid) fail("the view has no frame to query (draw one first).");
     if (q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
     for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
+    if (shade && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
     dev->use();
     query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
     if (count == 0) return;
@@ -2206,11 +2216,14 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     FrameParams R = P; R.traversalStack = nullptr;                    // the resolve reads the instance table and what it points to: no stack, no slab
     if (hostArrays) {
         // One round trip per chunk: [rays | hits] up as far as the call brings them, the kernels back to back, [hits | surfaces] down as far as the call wants them.
-        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE);
-        const size_t upB = rayB + (trace ? 0 : hitB), downB = ((trace && hits) ? hitB : 0) + (resolve ? surfB : 0);
+        static_assert(sizeof(RT64_RAY_MATERIAL) == sizeof(RT64_RAY_SURFACE), "one record size for both kinds of resolve");
+        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE), lodB = lods ? sizeof(float) : 0;
+        const size_t upB = rayB + (trace ? 0 : hitB) + lodB, downB = ((trace && hits) ? hitB : 0) + (resolve ? surfB : 0);
         const size_t chunk = std::min<size_t>(count, (size_t)1 << (resolve ? 18 : 20));
         dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB);
-        if (resolve) dev->querySurfaces.reserve(chunk * surfB);
+        DevArray<uint8_t> &records = shade ? dev->queryMaterials : dev->querySurfaces;
+        if (resolve) records.reserve(chunk * surfB);
+        if (lods) dev->queryLods.reserve(chunk * lodB);
         uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
         for (size_t at = 0; at < count; at += chunk) {
             const size_t n = std::min(chunk, count - at);
@@ -2220,17 +2233,24 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
                 memcpy(pin + n * rayB, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
                 HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, pin + n * rayB, n * hitB, hipMemcpyHostToDevice, s));
             }
+            if (lods) {
+                uint8_t *at4 = pin + n * (upB - lodB);
+                memcpy(at4, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, at4, n * lodB, hipMemcpyHostToDevice, s));
+            }
             if (trace) HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
-            if (resolve) HIP_CHECK(launch_hit_surface(R, dev->queryRays.ptr, dev->queryHits.ptr, dev->querySurfaces.ptr, n, s));
+            if (shade) HIP_CHECK(launch_hit_material(R, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
+            else if (resolve) HIP_CHECK(launch_hit_surface(R, dev->queryRays.ptr, dev->queryHits.ptr, records.ptr, n, s));
             uint8_t *down = pin;
             if (trace && hits) { HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
-            if (resolve) HIP_CHECK(hipMemcpyAsync(down, dev->querySurfaces.ptr, n * surfB, hipMemcpyDeviceToHost, s));
+            if (resolve) HIP_CHECK(hipMemcpyAsync(down, records.ptr, n * surfB, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
             if (trace && hits) memcpy(static_cast<uint8_t *>(hits) + at * hitB, pin, n * hitB);
             if (resolve) memcpy(static_cast<uint8_t *>(surfaces) + at * surfB, down, n * surfB);
         }
     }
     else if (trace) HIP_CHECK(launch_ray_query(P, rays, hits, count, flags, s));
+    else if (shade) HIP_CHECK(launch_hit_material(R, rays, hits, lods, surfaces, count, s));
     else HIP_CHECK(launch_hit_surface(R, rays, hits, surfaces, count, s));
     if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
     if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes and the vertex / index arrays) stay as they are until the query has run
@@ -2409,6 +2429,15 @@ RT64_EXPORT int RT64_ResolveViewRayHits(RT64_VIEW *view, const RT64_RAY *rays, c
 RT64_EXPORT int RT64_ResolveViewRayHitsDevice(RT64_VIEW *view, const void *rays, const void *hits, void *surfaces, size_t count, void *stream) {
     RT64_TRY run_view_query("RT64_ResolveViewRayHitsDevice", reinterpret_cast<View *>(view), rays, const_cast<void *>(hits), surfaces, count, 0, stream, false, QUERY_RESOLVE); return 1; RT64_CATCH(0)
 }
+RT64_EXPORT int RT64_ShadeViewRayHits(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, RT64_RAY_MATERIAL *materials, size_t count) {
+    RT64_TRY run_view_query("RT64_ShadeViewRayHits", reinterpret_cast<View *>(view), rays, const_cast<RT64_RAY_HIT *>(hits), materials, count, 0, nullptr, true, QUERY_SHADE, lods); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_ShadeViewRayHitsDevice(RT64_VIEW *view, const void *rays, const void *hits, const void *lods, void *materials, size_t count, void *stream) {
+    RT64_TRY run_view_query("RT64_ShadeViewRayHitsDevice", reinterpret_cast<View *>(view), rays, const_cast<void *>(hits), materials, count, 0, stream, false, QUERY_SHADE, lods); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayMaterials(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, RT64_RAY_MATERIAL *materials, size_t count, unsigned int flags) {
+    RT64_TRY run_view_query("RT64_TraceViewRayMaterials", reinterpret_cast<View *>(view), rays, hits, materials, count, flags, nullptr, true, QUERY_TRACE | QUERY_SHADE, lods); return 1; RT64_CATCH(0)
+}
 RT64_EXPORT int RT64_TraceViewRaySurfaces(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, RT64_RAY_SURFACE *surfaces, size_t count, unsigned int flags) {
     RT64_TRY run_view_query("RT64_TraceViewRaySurfaces", reinterpret_cast<View *>(view), rays, hits, surfaces, count, flags, nullptr, true, QUERY_TRACE | QUERY_RESOLVE); return 1; RT64_CATCH(0)
 }
@@ -2489,7 +2518,19 @@ RT64_EXPORT RT64_TEXTURE *RT64_CreateTexture(RT64_DEVICE *devicePtr, RT64_TEXTUR
     return reinterpret_cast<RT64_TEXTURE *>(t);
     } catch (const std::exception &e) { GlobalLastError = e.what(); fprintf(stderr, "%s\n", e.what()); delete t; return nullptr; }
 }
-RT64_EXPORT void RT64_DestroyTexture(RT64_TEXTURE *texture) { RT64_TRY Texture *t = reinterpret_cast<Texture *>(texture); if (t) { t->device->enter(); t->device->beforeSceneMutation(); hipStreamSynchronize(t->device->stream); } delete t; RT64_CATCH_VOID }
+RT64_EXPORT void RT64_DestroyTexture(RT64_TEXTURE *texture) {
+    RT64_TRY
+    Texture *t = reinterpret_cast<Texture *>(texture);
+    if (t) {
+        Device *dev = t->device;
+        dev->enter(); dev->beforeSceneMutation(); hipStreamSynchronize(dev->stream);
+        try { dev->awaitQueries(); } catch (...) {}          // a material query on a caller stream may still read the texels (H11)
+        for (Scene *sc : dev->scenes) for (View *v : sc->views)
+            for (auto &e : v->query.textures) if (e.first == t && e.second == t->serial) { v->query.textureDestroyed = true; e.first = nullptr; }
+    }
+    delete t;
+    RT64_CATCH_VOID
+}
 
 // Debug readback of a texture's texels as the kernels sample them (additive): RGBA8, mip `mip`, rows top to bottom -- for a BC7 DDS what bc7_decode_kernel
 // wrote at creation (rt64_texture.cpp:146-187 hands the blocks to the sampler hardware; here they are decoded once).  dst = NULL returns the size.

@@ -235,6 +235,14 @@ SURFACE_API = [
     ("TraceViewRaySurfaces", "RT64_TraceViewRaySurfaces", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint]),
 ]
 SURFACE_VALID, SURFACE_BACK_FACE, SURFACE_HAS_UV, SURFACE_BAD_HIT = 0x1, 0x2, 0x4, 0x8
+# include/rt64_material.h: material records for hits, a list and a loader (RT64_LoadLibraryMaterial) of its own as well
+MATERIAL_API = [
+    ("ShadeViewRayHits", "RT64_ShadeViewRayHits", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t]),
+    ("ShadeViewRayHitsDevice", "RT64_ShadeViewRayHitsDevice", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewRayMaterials", "RT64_TraceViewRayMaterials", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+(MATERIAL_VALID, MATERIAL_BAD_HIT, MATERIAL_TEXTURED, MATERIAL_NORMAL_MAPPED, MATERIAL_SPECULAR_MAPPED, MATERIAL_CUTOUT, MATERIAL_SHADOW_CUTOUT,
+ MATERIAL_NOISE_ALPHA, MATERIAL_BACK_FACE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x100
 
 
 class RAY(C.Structure):
@@ -251,7 +259,12 @@ class RAY_SURFACE(C.Structure):
                 ("shadingNormal", C.c_float * 3), ("primitive", C.c_uint), ("uv", C.c_float * 2), ("t", C.c_float), ("reserved", C.c_uint)]
 
 
-assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64
+class RAY_MATERIAL(C.Structure):
+    _fields_ = [("color", C.c_float * 4), ("shadingNormal", C.c_float * 3), ("flags", C.c_uint), ("specular", C.c_float * 3), ("shadowAlpha", C.c_float),
+                ("lod", C.c_float), ("instance", C.c_int), ("primitive", C.c_uint), ("reserved", C.c_uint)]
+
+
+assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
 
 HALO_ROWS = 62
 HALO_BYTES_PER_PIXEL = 24
@@ -276,7 +289,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -357,5 +370,61 @@ def trace_surfaces(lib, view, rays, flags=0):
         raise ValueError("rays: an (N, 8) float32 array")
     hits, out = np.empty_like(rays), np.empty((rays.shape[0], 16), dtype=np.float32)
     if not lib.TraceViewRaySurfaces(view, rays.ctypes.data, hits.ctypes.data, out.ctypes.data, rays.shape[0], flags):
+        raise RuntimeError(lib.last_error())
+    return hits, out
+
+
+def shade_hits(lib, view, rays, hits, lods=None, stream=None):
+    """RT64_ShadeViewRayHits: (N, 8) float32 rays, the (N, 8) float32 hits trace_rays returned for them and, optionally, (N,) float32 lods
+    (None: level 0 for every record) -> (N, 16) float32 RT64_RAY_MATERIALs: color rgba, shadingNormal xyz, flags, specular xyz, shadowAlpha,
+    lod, instance, primitive, reserved (flags, instance, primitive as uint32 / int32 bits: read them through `.view(int32)`).  NumPy arrays
+    take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    if type(rays).__module__.split(".")[0] == "torch":
+        import torch
+        for a in (rays, hits):
+            if a.dim() != 2 or a.shape[1] != 8 or a.dtype != torch.float32 or not a.is_cuda:
+                raise ValueError("rays, hits: (N, 8) float32 CUDA tensors")
+        if rays.shape[0] != hits.shape[0]:
+            raise ValueError("one hit per ray")
+        if lods is not None:
+            if lods.dim() != 1 or lods.shape[0] != rays.shape[0] or lods.dtype != torch.float32 or not lods.is_cuda:
+                raise ValueError("lods: an (N,) float32 CUDA tensor")
+            lods = lods.contiguous()
+        rays, hits = rays.contiguous(), hits.contiguous()
+        out = torch.empty((rays.shape[0], 16), dtype=torch.float32, device=rays.device)
+        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+        if s != torch.cuda.current_stream(rays.device):
+            for a in (rays, hits, out) + ((lods,) if lods is not None else ()):
+                a.record_stream(s)
+        ok = lib.ShadeViewRayHitsDevice(view, rays.data_ptr(), hits.data_ptr(), lods.data_ptr() if lods is not None else None, out.data_ptr(), rays.shape[0], s.cuda_stream)
+    else:
+        import numpy as np
+        rays, hits = np.ascontiguousarray(rays, dtype=np.float32), np.ascontiguousarray(hits, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != rays.shape:
+            raise ValueError("rays, hits: (N, 8) float32 arrays of one length")
+        if lods is not None:
+            lods = np.ascontiguousarray(lods, dtype=np.float32)
+            if lods.shape != (rays.shape[0],):
+                raise ValueError("lods: an (N,) float32 array")
+        out = np.empty((rays.shape[0], 16), dtype=np.float32)
+        ok = lib.ShadeViewRayHits(view, rays.ctypes.data, hits.ctypes.data, lods.ctypes.data if lods is not None else None, out.ctypes.data, rays.shape[0])
+    if not ok:
+        raise RuntimeError(lib.last_error())
+    return out
+
+
+def trace_materials(lib, view, rays, lods=None, flags=0):
+    """RT64_TraceViewRayMaterials on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): trace and shade in one staging
+    round trip -> (hits (N, 8), materials (N, 16))."""
+    import numpy as np
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("rays: an (N, 8) float32 array")
+    if lods is not None:
+        lods = np.ascontiguousarray(lods, dtype=np.float32)
+        if lods.shape != (rays.shape[0],):
+            raise ValueError("lods: an (N,) float32 array")
+    hits, out = np.empty_like(rays), np.empty((rays.shape[0], 16), dtype=np.float32)
+    if not lib.TraceViewRayMaterials(view, rays.ctypes.data, hits.ctypes.data, lods.ctypes.data if lods is not None else None, out.ctypes.data, rays.shape[0], flags):
         raise RuntimeError(lib.last_error())
     return hits, out

@@ -68,6 +68,7 @@ class InstanceData:
     flags: int = 0
     scissor: Optional[tuple] = None  # RT64_RECT (x, y, w, h), origin bottom-left; None = unset
     viewport: Optional[tuple] = None
+    shader: Optional[tuple] = None   # (shaderId, filter, hAddr, vAddr, flags) of a shader of its own; None = the scene's shader
 
 
 @dataclass
@@ -341,6 +342,7 @@ class Rt64Scene:
         self.shader = lib.CreateShader(self.device, data.shader_id, data.shader_filter, data.shader_haddr, data.shader_vaddr, data.shader_flags)
         if not self.shader:
             raise RuntimeError("RT64_CreateShader failed: " + lib.last_error())
+        self._own_shaders = {}           # InstanceData.shader tuple -> handle
         self._lights = (rt64.LIGHT * len(data.lights))(*data.lights)
         self.view = lib.CreateView(self.scene)
         self.textures = []
@@ -383,6 +385,14 @@ class Rt64Scene:
         d.normalTexture = self.textures[inst.normal] if inst.normal is not None else None
         d.specularTexture = self.textures[inst.specular] if inst.specular is not None else None
         d.shader = self.shader
+        if inst.shader is not None:
+            key = tuple(int(x) for x in inst.shader)
+            if key not in self._own_shaders:
+                h = self.lib.CreateShader(self.device, *key)
+                if not h:
+                    raise RuntimeError("RT64_CreateShader failed: " + self.lib.last_error())
+                self._own_shaders[key] = h
+            d.shader = self._own_shaders[key]
         d.material = inst.material
         d.flags = inst.flags
         if inst.scissor:
@@ -458,6 +468,8 @@ class Rt64Scene:
             for h in self.textures:
                 self.lib.DestroyTexture(h)
             self.lib.DestroyShader(self.shader)
+            for h in self._own_shaders.values():
+                self.lib.DestroyShader(h)
             self.lib.DestroyDevice(self.device)        # deletes scenes -> views + instances (rt64_device.cpp:97-100)
             self.device = None
 

@@ -33,6 +33,7 @@
 #include <zlib.h>
 
 #include "rt64.h"
+#include "rt64_material.h"        /* (includes rt64_surface.h and rt64_query.h) */
 
 typedef struct { RT64_VECTOR4 position; RT64_VECTOR3 normal; RT64_VECTOR2 uv; RT64_VECTOR4 input1; } VERTEX;   /* main.cpp:36-41, 52 bytes */
 
@@ -381,6 +382,17 @@ int main(int argc, char **argv) {
     if (RT64.ext.GetDeviceStats && RT64.ext.GetDeviceStats(RT64.device, &st)) gpuMs = st.msTotal;
     printf("{\"host\": \"C (tools/sample_host.c)\", \"width\": %d, \"height\": %d, \"frames\": %d, \"ranks\": %d, \"checksum\": %llu, \"fnv1a\": \"%016llx\", \"picked_center\": \"%s\", \"gpu_ms_last_frame\": %.4f, \"ms_per_frame\": %.5f}\n",
            width, height, frames, ranks, sum, fnv, pickedName, gpuMs, msPerFrame);
+    if (ranks == 0) {       /* what does the surface in front of the camera look like?  One ray through RT64_TraceViewRayMaterials (rt64_material.h), after the frame */
+        RT64_LIBRARY_MATERIAL mat = RT64_LoadLibraryMaterial(RT64.lib);
+        RT64_RAY ray; RT64_RAY_HIT hit; RT64_RAY_MATERIAL m;
+        memset(&ray, 0, sizeof(ray));
+        ray.origin[0] = -RT64.viewMatrix.m[3][0]; ray.origin[1] = -RT64.viewMatrix.m[3][1]; ray.origin[2] = -RT64.viewMatrix.m[3][2];       /* the view is a translation (main.cpp:250-258) */
+        ray.direction[2] = -1.0f; ray.tMin = 0.0f; ray.tMax = INFINITY;
+        if (!mat.TraceViewRayMaterials) fprintf(stderr, "sample_host: librt64.so lacks RT64_TraceViewRayMaterials\n");
+        else if (!mat.TraceViewRayMaterials(RT64.view, &ray, &hit, NULL, &m, 1, 0)) fprintf(stderr, "sample_host: TraceViewRayMaterials: %s\n", RT64.lib.GetLastError());
+        else printf("material probe: t %.4f instance %d color %.4f %.4f %.4f %.4f specular %.4f %.4f %.4f shadowAlpha %.4f flags 0x%03x\n", hit.t, m.instance,
+                    m.color[0], m.color[1], m.color[2], m.color[3], m.specular[0], m.specular[1], m.specular[2], m.shadowAlpha, m.flags);
+    }
     if (dump) { FILE *f = fopen(dump, "wb"); if (f) { fwrite(frame, 1, bytes, f); fclose(f); } }
     free(frame);
 
