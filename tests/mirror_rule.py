@@ -36,17 +36,17 @@ MUTATIONS = ("fresnel_from_hit", "fresnel_no_floor", "mirror_fog_from_camera", "
 
 # ---- helpers ---------------------------------------------------------------------------------------------------------------------------------
 
-def _take(f, idx):
+def take(f, idx):
     return F(f.v[idx], f.e[idx])
 
 
-def _put(dst, mask, src):
+def put(dst, mask, src):
     """dst where ~mask, src (already of mask.sum() values) where mask."""
     v = dst.v.copy(); e = np.array(dst.e, dtype=np.float64); v[mask] = src.v; e[mask] = src.e
     return F(v, e)
 
 
-def _unorm8(x):
+def unorm8(x):
     """A material constant in [0, 1] as the hit record's RGBA8 stores it: (value k / 255 as F, tie): k = round(255 x); tie where float32 could round the other way."""
     y = np.clip(np.asarray(x, dtype=np.float64), 0.0, 1.0) * 255.0
     k = np.rint(y)
@@ -55,13 +55,13 @@ def _unorm8(x):
     return F(v, np.where((k == 0) | (k == 255), 0.0, 2.0 * L.U * v)), tie
 
 
-def _fmin(a, c):
+def fmin(a, c):
     v = np.minimum(a.v, c)
     return F(v, np.maximum(np.minimum(a.v + a.e, c) - v, v - np.minimum(a.v - a.e, c)))
 
 
-def _clamp(a, lo, hi):
-    return _fmin(L.fmax(a, lo), hi)
+def clamp(a, lo, hi):
+    return fmin(L.fmax(a, lo), hi)
 
 
 def scene_triangles(scene):
@@ -120,7 +120,7 @@ def hit_lists(scene, origin, direction, mutate=None, chunk=512):
     return res
 
 
-def _hit_normals(scene, tri, u, v, du, dv, front):
+def hit_normals(scene, tri, u, v, du, dv, front):
     """Shading normal of hits (one per ray): the vertex normals interpolated by (1 - u - v, u, v), through the instance's normal matrix, renormalised, turned against the
     ray (rt64_shader.cpp:518-521; tests/surface_rule.py A7), then SNORM16: the value is kept unrounded and the bound takes half a step."""
     import surface_rule as S
@@ -142,11 +142,11 @@ def _hit_normals(scene, tri, u, v, du, dv, front):
         sign = np.where(front[sel], 1.0, -1.0)
         for c in range(3):
             x = F(sn[c].v * sign, sn[c].e + SNORM16_HALF_STEP)
-            out[c] = _put(out[c], inst[tri] == k, x)
+            out[c] = put(out[c], inst[tri] == k, x)
     return out
 
 
-def _hit_colours(scene, tri, u, v, du, dv, mutate=None):
+def hit_colours(scene, tri, u, v, du, dv, mutate=None):
     """Colour of hits as the hit record's RGBA8 holds it: three F, a tie mask and which hits took a texel.  diffuseColorMix.w = 1: the mix colour.  w = 0 on an instance
     with a `texture` (levels, uv (T, 3, 2), filter, ha, va): the texel of tests/sampler_rule.py at zero gradients (lod 0) at the interpolated uv, whose error is that of the
     barycentrics through the corners' uv differences; `sample_grad_bounds` gives the lowest and highest byte a float32 sampler may store over that box, and the colour is
@@ -163,7 +163,7 @@ def _hit_colours(scene, tri, u, v, du, dv, mutate=None):
         mix = I["material"]["diffuseColorMix"]
         if mix[3] == 1.0:
             for c in range(3):
-                q, t = _unorm8(np.full(int(here.sum()), mix[c])); col[c] = _put(col[c], here, q); tie[here] |= t
+                q, t = unorm8(np.full(int(here.sum()), mix[c])); col[c] = put(col[c], here, q); tie[here] |= t
             continue
         T = I.get("texture")
         assert mix[3] == 0.0 and T is not None, "a surface takes its colour from diffuseColorMix with w = 1, or from its texture with w = 0"
@@ -176,19 +176,19 @@ def _hit_colours(scene, tri, u, v, du, dv, mutate=None):
         lo, hi = r["lo"].astype(np.float64), r["hi"].astype(np.float64)
         for c in range(3):
             mid = 0.5 * (lo[:, c] + hi[:, c]) / 255.0
-            col[c] = _put(col[c], here, F(mid, 0.5 * (hi[:, c] - lo[:, c]) / 255.0 + 2.0 * L.U * mid))
+            col[c] = put(col[c], here, F(mid, 0.5 * (hi[:, c] - lo[:, c]) / 255.0 + 2.0 * L.U * mid))
         textured[here] = True
     return col, tie, textured
 
 
 # ---- fog (Fog:5-27) --------------------------------------------------------------------------------------------------------------------------
 
-def _fog_from_origin(position, origin, mul_, offset):
+def fog_from_origin(position, origin, mul_, offset):
     distance = L.length3(L.sub3(position, origin))
     return L.saturate(L.mul(L.div(L.add(distance, offset), mul_), 0.5))
 
 
-def _fog_from_camera(position, view_proj, mul_, offset):
+def fog_from_camera(position, view_proj, mul_, offset):
     """(Fog:5-18) clip = p * viewProj; z = 2 z - w; alpha = saturate((z / max(w, 0.001) * fogMul + fogOffset) / 255).  viewProj: 4 x 4 float64; its float32 entries are taken as
     CAM_K roundings off.  The position's own error moves clip.z and clip.w together, so it is taken through the quotient's gradient (first order, as every bound here)
     instead of through the two sums separately; the roundings of the evaluation are those of the F arithmetic on the position's value."""
@@ -247,25 +247,25 @@ def _resolve(scene, origin, direction, alpha_in, parent_inst, glass, mutate):
         why["facing"][rows] |= ~culled & ~g("front_decided").astype(bool)
         k = len(rows)
         # colour and alpha as the hit record holds them (UNORM8)
-        col, tie, tex_here = _hit_colours(scene, tri, g("u"), g("v"), g("du"), g("dv"), mutate)
+        col, tie, tex_here = hit_colours(scene, tri, g("u"), g("v"), g("du"), g("dv"), mutate)
         why["tie"][rows] |= tie
         tex_seen = tex_here
-        h_alpha, tie = _unorm8(tab("solidAlphaMultiplier")[inst]); why["tie"][rows] |= tie
-        ra = _take(res_a, rows)
+        h_alpha, tie = unorm8(tab("solidAlphaMultiplier")[inst]); why["tie"][rows] |= tie
+        ra = take(res_a, rows)
         contrib = L.mul(ra, h_alpha)
         why["gate"][rows] |= np.abs(contrib.v - EPSILON) < DECISION_K * contrib.e
         passes = contrib.v >= EPSILON                                                                              # (M:75-76)
         # where the hit lies: origin + direction * ((t - bias) + bias)
         tF = F(g("t"), g("dt") + 2.0 * L.U * np.abs(g("t")))
-        d_r = [_take(c, rows) for c in direction]; o_r = [_take(c, rows) for c in origin]
+        d_r = [take(c, rows) for c in direction]; o_r = [take(c, rows) for c in origin]
         pos = L.add3(o_r, L.scale3(d_r, tF))
-        nrm = _hit_normals(scene, tri, g("u"), g("v"), g("du"), g("dv"), g("front").astype(bool) | culled | (mutate == "no_flip"))
+        nrm = hit_normals(scene, tri, g("u"), g("v"), g("du"), g("dv"), g("front").astype(bool) | culled | (mutate == "no_flip"))
         spec = [L.mul(F(np.asarray([m_["material"]["specularColor"][c] for m_ in mats], dtype=np.float64)[inst]), 1.0) for c in range(3)]
         fog_on = tab("fogEnabled")[inst] != 0
         if fog_on.any():                                                                                          # (M:82-86, G:78-82)
             fm, fo = np.where(fog_on, tab("fogMul")[inst], 1.0), np.where(fog_on, tab("fogOffset")[inst], 0.0)
             from_camera = glass != (mutate == "mirror_fog_from_camera")
-            fa = _fog_from_camera(pos, scene["viewProj"], fm, fo) if from_camera else _fog_from_origin(pos, o_r, fm, fo)
+            fa = fog_from_camera(pos, scene["viewProj"], fm, fo) if from_camera else fog_from_origin(pos, o_r, fm, fo)
             fa = L.where(fog_on, fa, 0.0)
             fc = np.asarray([m_["material"]["fogColor"] for m_ in mats], dtype=np.float64)[inst]
             add_t = [L.mul(F(fc[:, c]), L.mul(fa, contrib)) for c in range(3)]
@@ -274,20 +274,20 @@ def _resolve(scene, origin, direction, alpha_in, parent_inst, glass, mutate):
             add_t = [F(np.zeros(k)) for _ in range(3)]; contrib_f = contrib
         lit = np.asarray([int(m_["material"]["lightGroupMaskBits"]) for m_ in mats], dtype=np.int64)[inst] > 0        # (M:78)
         self_light = np.asarray([m_["material"]["selfLight"] for m_ in mats], dtype=np.float64)[inst]
-        na = _take(new_alpha, rows)
+        na = take(new_alpha, rows)
         if not glass:                                                                                             # (M:19-23, 91-96)
             rf = tab("reflectionFactor")[inst]
             mirrors = rf > EPSILON
             ff = tab("reflectionFresnelFactor")[inst] if mutate == "fresnel_from_hit" else parent_fresnel[rows]    # sic: the MIRRORING instance's factor (M:93)
             base = L.add(1.0, L.dot3(nrm, d_r))
-            ret = L.power(_clamp(base, EPSILON, 1.0), 5.0)
+            ret = L.power(clamp(base, EPSILON, 1.0), 5.0)
             if mutate == "fresnel_no_floor":                                                                       # pow of a negative base is not a number in HLSL
                 ret = F(np.where(base.v < 0.0, np.nan, ret.v), ret.e)
             fres = L.add(rf, L.mul(L.mul(L.sub(1.0, rf), ret), ff))
-            na = L.where(passes & mirrors, L.add(na, L.mul(L.mul(fres, contrib_f), _take(alpha_in, rows))), na)
+            na = L.where(passes & mirrors, L.add(na, L.mul(L.mul(fres, contrib_f), take(alpha_in, rows))), na)
         new_rgb, new_t = [], []
         for c in range(3):
-            r_c, t_c = _take(res_rgb[c], rows), _take(transparent[c], rows)
+            r_c, t_c = take(res_rgb[c], rows), take(transparent[c], rows)
             t_c = L.where(passes, L.add(t_c, add_t[c]), t_c)
             lit_add = L.add(r_c, L.mul(col[c], contrib_f))
             unlit_add = L.add(t_c, L.mul(L.mul(col[c], contrib_f), L.add(ambient[c], F(self_light[:, c]))))
@@ -298,14 +298,14 @@ def _resolve(scene, origin, direction, alpha_in, parent_inst, glass, mutate):
         ra_new = L.where(passes, L.mul(ra, L.sub(1.0, h_alpha)), ra)
         # write back
         for c in range(3):
-            res_rgb[c] = _put(res_rgb[c], has, new_rgb[c]); transparent[c] = _put(transparent[c], has, new_t[c])
-            st_pos[c] = _put(st_pos[c], has, L.where(keeps, pos[c], _take(st_pos[c], rows)))
-            st_nrm[c] = _put(st_nrm[c], has, L.where(keeps, nrm[c], _take(st_nrm[c], rows)))
-            st_spec[c] = _put(st_spec[c], has, L.where(keeps, spec[c], _take(st_spec[c], rows)))
+            res_rgb[c] = put(res_rgb[c], has, new_rgb[c]); transparent[c] = put(transparent[c], has, new_t[c])
+            st_pos[c] = put(st_pos[c], has, L.where(keeps, pos[c], take(st_pos[c], rows)))
+            st_nrm[c] = put(st_nrm[c], has, L.where(keeps, nrm[c], take(st_nrm[c], rows)))
+            st_spec[c] = put(st_spec[c], has, L.where(keeps, spec[c], take(st_spec[c], rows)))
         st_id[rows] = np.where(keeps, inst, st_id[rows])
         contributing[rows] += passes; textured[rows] |= passes & tex_seen
-        new_alpha = _put(new_alpha, has, na)
-        res_a = _put(res_a, has, ra_new)
+        new_alpha = put(new_alpha, has, na)
+        res_a = put(res_a, has, ra_new)
         why["gate"][rows] |= passes & (np.abs(ra_new.v - EPSILON) < DECISION_K * ra_new.e)
         stop = np.zeros(n, dtype=bool); stop[rows] = ra_new.v <= EPSILON                                           # (M:112)
         alive = alive & ~stop
@@ -325,8 +325,8 @@ def _lights(scene, R, direction, px, py, check_shadows, mutate):
     ids = R["id"][idx]
     mats = [I["material"] for I in scene["instances"]]
     tab = lambda key: np.asarray([m[key] for m in mats], dtype=np.float64)[ids]
-    st = {"position": [_take(c, idx) for c in R["pos"]], "normal": [_take(c, idx) for c in R["nrm"]], "specular": [_take(c, idx) for c in R["spec"]],
-          "rayDirection": [_take(c, idx) for c in direction], "px": px[idx], "py": py[idx], "bluenoise": scene["bluenoise"], "frameCount": int(scene["frameCount"]),
+    st = {"position": [take(c, idx) for c in R["pos"]], "normal": [take(c, idx) for c in R["nrm"]], "specular": [take(c, idx) for c in R["spec"]],
+          "rayDirection": [take(c, idx) for c in direction], "px": px[idx], "py": py[idx], "bluenoise": scene["bluenoise"], "frameCount": int(scene["frameCount"]),
           "diSamples": int(scene["diSamples"]), "shadow": scene.get("shadow"), "checkShadows": check_shadows,
           "ignoreNormalFactor": tab("ignoreNormalFactor"), "specularExponent": tab("specularExponent"), "shadowRayBias": tab("shadowRayBias")}
     mask = np.asarray([int(m["lightGroupMaskBits"]) for m in mats], dtype=np.uint32)[ids]
@@ -338,7 +338,7 @@ def _lights(scene, R, direction, px, py, check_shadows, mutate):
         lam = L.fmax(L.dot3(nrm, L.neg3(rd)), 0.0)
         res = [L.add(a, L.mul(float(scene["eyeDiffuse"][c]), lam)) for c, a in enumerate(res)]
     for c in range(3):
-        light[c] = _put(light[c], have, res[c])
+        light[c] = put(light[c], have, res[c])
     for k in why:
         why[k][idx] = w[k]
     return light, why, have

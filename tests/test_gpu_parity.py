@@ -56,6 +56,9 @@ def test_traversal_counters_match_oracle(scene_256, oracle_256):
 
 
 def test_gbuffer_parity(scene_256, oracle_256):
+    """The G-buffer of the sample scene against the oracle's.  Its flow line is on a STATIC frame (still camera, previousTransform = transform), where every value is 0
+    or near it, and its depth line on that one frame: flow with a moving camera, moving instances, a jittered frame and a canReproject = false frame, depth, the masks
+    and the loop's bookkeeping are held pixel by pixel to the float64 rule of tests/primary_rule.py in tests/test_gpu_primary_rule.py."""
     from sm64rt_legacy_renderer_amd import rt64
     _, ref = oracle_256
     pos = scene_256.readback(rt64.IMAGE_SHADING_POSITION)
