@@ -75,9 +75,12 @@ def scene_triangles(scene):
 
 # ---- the hit list (M2-M3) --------------------------------------------------------------------------------------------------------------------
 
-def hit_lists(scene, origin, direction, mutate=None, chunk=512):
+def hit_lists(scene, origin, direction, mutate=None, chunk=512, origin_e=None, direction_e=None):
     """Every ray against every triangle, float64 brute force (light_rule.triangle_test, margins of BruteForceShadows).  A hit needs tmin 0.1 < t < 100000 and, unless
     its instance disables culling, a front face: det = e1 . (d x e2) > 0.  Hits are ordered by t - depthBias (I:17-19).
+    origin_e (N,), direction_e (N, 3): by how much a ray's origin (a length) and direction (per component) may themselves be off (a ray that starts from computed
+    values, tests/gi_rule.py); they widen the margins to first order: the numerators of u, v, t move by at most |do| |d| |e| + |tv| |dd| |e|, det by |dd| |e1| |e2|.
+    With them a ray parallel to a triangle's plane, exactly or beyond the triangle's reach, is a decided miss (the two tests are explained where they stand).
 
     Returns dict: count (N,), decided (N,) -- every triangle a decided hit or a decided miss -- and per slot (N, M): tri (index into scene_triangles), u, v, t, du, dv, dt,
     key, key_e, front (bool), front_decided (bool)."""
@@ -93,13 +96,38 @@ def hit_lists(scene, origin, direction, mutate=None, chunk=512):
         u, v, t, du, dv, dt, det, ok = L.triangle_test(v0, e1, e2, o, d)
         w = 1.0 - u - v
         det_e = L.SHADOW_K * L.U * np.linalg.norm(d, axis=1)[:, None] * (l1 * l2)[None]
+        parallel = np.zeros(det.shape, dtype=bool)
+        if origin_e is not None:
+            oe, dc = np.asarray(origin_e)[a:a + chunk, None], np.abs(np.asarray(direction_e)[a:a + chunk])
+            de = np.linalg.norm(dc, axis=1)[:, None]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                inv = 1.0 / np.abs(det)
+                move = oe * np.linalg.norm(d, axis=1)[:, None] + np.linalg.norm(o[:, None, :] - v0[None], axis=2) * de
+                rel = de * (l1 * l2)[None] * inv
+                du = du + move * l2[None] * inv + np.abs(u) * rel
+                dv = dv + move * l1[None] * inv + np.abs(v) * rel
+                dt = dt + oe * (l1 * l2)[None] * inv + np.abs(t) * rel
+            ok = ok & np.isfinite(du) & np.isfinite(dv) & np.isfinite(dt)
+            det_e = det_e + de * (l1 * l2)[None]
+            # det = e1 . (d x e2) is a sum of six products e1_i d_j e2_k.  Where every one of them has a factor that is exactly zero (a ray along an axis-aligned face: the
+            # component of d itself and its error are zero) every float32 evaluation gives 0 too, and det == 0 is a miss (oracle_trace.c R3; an exact parallel never meets the plane)
+            a1, a2, ad = np.abs(e1)[None], np.abs(e2)[None], (np.abs(d) + dc)[:, None, :]
+            size = sum(a1[..., i] * (ad[..., j] * a2[..., k] + ad[..., k] * a2[..., j]) for i, j, k in ((0, 1, 2), (1, 2, 0), (2, 0, 1)))
+            parallel = size == 0.0
+            # a ray all but parallel to a triangle's plane whose sign of det float32 cannot tell: it meets the plane no nearer than |t| >= (|num| - its error) / (|det| +
+            # its error), num = e2 . (tv x e1); a triangle reaches no farther from the origin than |tv| + |e1| + |e2|: beyond that, a miss whatever the sign
+            tvv = o[:, None, :] - v0[None]
+            T = np.linalg.norm(tvv, axis=2)
+            num = np.abs(np.einsum("ntk,ntk->nt", np.broadcast_to(e2[None], tvv.shape), np.cross(tvv, e1[None])))
+            num_e = (L.SHADOW_K * L.U * (T + (np.linalg.norm(o, axis=1)[:, None] + np.linalg.norm(v0, axis=1)[None]) / L.SHADOW_K) + oe) * (l1 * l2)[None]
+            parallel |= (num - num_e) * np.linalg.norm(d, axis=1)[:, None] > (np.abs(det) + det_e) * 2.0 * (T + (l1 + l2)[None])
         front, front_dec = det > 0.0, np.abs(det) > det_e
         facing_ok = ~cull[None] | (front & front_dec)
         facing_no = cull[None] & ~front & front_dec
         inside = (u > du) & (v > dv) & (w > du + dv) & (t > L.RAY_MIN_DISTANCE + dt) & (t < RAY_MAX_DISTANCE - dt)
         outside = (u < -du) | (v < -dv) | (w < -(du + dv)) | (t < L.RAY_MIN_DISTANCE - dt) | (t > RAY_MAX_DISTANCE + dt)
-        hit = ok & inside & facing_ok
-        miss = (ok & outside) | facing_no          # (a ray within rounding of a triangle's plane is decided only by another test)
+        hit = ok & inside & facing_ok & ~parallel
+        miss = (ok & outside) | facing_no | parallel          # (a ray within rounding of a triangle's plane is decided only by another test)
         decided[a:a + chunk] = (hit | miss).all(axis=1)
         counts[a:a + chunk] = hit.sum(axis=1)
         key = np.where(hit, (t if mutate == "order_by_t" else t - bias[None]), np.inf)
