@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
-#include "../../include/rt64_material.h"     // (includes rt64_surface.h and rt64_query.h)
+#include "../../include/rt64_alpha.h"        // (includes rt64_material.h, rt64_surface.h and rt64_query.h)
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -160,3 +160,9 @@ hipError_t launch_rcas_sharpen(const float *in, float *out, int dw, int dh, floa
 // Rank 0 of a multi-GPU gather: frame row y <- row gather_row_owner(y) of the owner's packed buffer (`own` for rank 0, bucket + r * slotBytes for rank r).
 hipError_t launch_gather_assemble(const uint8_t *own, const uint8_t *bucket, size_t slotBytes, uint8_t *frame, int width, const GatherLayout &L, hipStream_t s);
 hipError_t launch_row_hit_count(const int32_t *hitInstance, uint32_t *counts, int width, int height, hipStream_t s);      // counts[y] = pixels of row y whose primary ray hit geometry
+
+// ---- alpha_query.hip -----------------------------------------------------------------------------------------------
+// RT64_TraceViewRaysAlpha: `count` RT64_RAYs and (lods != nullptr) one float lod per ray -> RT64_RAY_HITs; RT64_TraceViewRayVisibility: RT64_RAYs -> RT64_RAY_VISIBILITYs
+// (device pointers, 16-byte aligned; lods 4) against the tables of P (rules K1-K10).  P.traversalStack as for launch_ray_query; both read the texture table of P as well.
+hipError_t launch_alpha_query(const FrameParams &P, const void *rays, const void *lods, void *hits, uint64_t count, uint32_t flags, hipStream_t s);
+hipError_t launch_visibility_query(const FrameParams &P, const void *rays, void *visibility, uint64_t count, uint32_t flags, hipStream_t s);

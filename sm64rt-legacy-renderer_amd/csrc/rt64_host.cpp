@@ -225,7 +225,7 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials;
+    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility;
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -448,7 +448,7 @@ struct View {
     struct QueryScene {
         bool valid = false;                       // a frame was drawn (a refused frame clears it: View::discardUpdate)
         bool meshDestroyed = false;               // RT64_DestroyMesh on a mesh that frame traced
-        bool textureDestroyed = false;            // RT64_DestroyTexture on a texture that frame's table holds (material records only: H11)
+        bool textureDestroyed = false;            // RT64_DestroyTexture on a texture that frame's table holds (material records and the walks that honour alpha: H11, K9)
         FrameParams P;                            // instances, TLAS, LDS scene-cache image of the frame's table slot
         int slot = 0; bool needSpill = false;
         std::vector<std::pair<Mesh *, uint32_t>> meshes;      // the meshes the frame traced and the version (RT64_SetMesh count) it traced
@@ -2169,21 +2169,26 @@ static void query_overflow_check(Device *dev, const char *fn) {
 }
 
 // What one call does with its records: the walk (query.hip), the surface records of hits (surface.hip), or both back to back.
-enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2, QUERY_SHADE = 4 };
+// QUERY_ALPHA / QUERY_VISIBILITY: walks that run the any-hit programs themselves (alpha_query.hip); each stands alone in `work`.
+enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2, QUERY_SHADE = 4, QUERY_ALPHA = 8, QUERY_VISIBILITY = 16 };
 
 // hostArrays: rays / hits / surfaces in host memory, staged in chunks through pinned memory on the device's stream.  Otherwise device arrays, on `stream` (NULL: the device's stream).
 // work = QUERY_TRACE: rays -> hits (RT64_TraceViewRays).  QUERY_RESOLVE: rays + hits -> surfaces (RT64_ResolveViewRayHits).  Both: rays -> hits -> surfaces, host arrays only,
 // and `hits` may be NULL (RT64_TraceViewRaySurfaces).  QUERY_SHADE in place of QUERY_RESOLVE: `surfaces` holds RT64_RAY_MATERIALs and `lods` (or NULL) travels with the rays
-// (RT64_ShadeViewRayHits, RT64_TraceViewRayMaterials; material.hip).
+// (RT64_ShadeViewRayHits, RT64_TraceViewRayMaterials; material.hip).  QUERY_ALPHA: rays (+ lods) -> hits (RT64_TraceViewRaysAlpha).  QUERY_VISIBILITY: rays -> RT64_RAY_VISIBILITYs,
+// handed in as `hits` (RT64_TraceViewRayVisibility).  Both read the texture table like QUERY_SHADE (K9).
 static void run_view_query(const char *fn, View *v, const void *rays, void *hits, void *surfaces, size_t count, unsigned flags, void *stream, bool hostArrays, int work, const void *lods = nullptr) {
     auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool alpha = (work & QUERY_ALPHA) != 0, visibility = (work & QUERY_VISIBILITY) != 0, walk = (work & (QUERY_TRACE | QUERY_ALPHA | QUERY_VISIBILITY)) != 0;
     const bool trace = (work & QUERY_TRACE) != 0, shade = (work & QUERY_SHADE) != 0, resolve = (work & (QUERY_RESOLVE | QUERY_SHADE)) != 0;
     if (!v) fail("NULL view.");
-    if (!resolve) { if (!rays || !hits) fail("NULL ray or hit array."); }
+    if (visibility) { if (!rays || !hits) fail("NULL ray or visibility array."); }
+    else if (!resolve) { if (!rays || !hits) fail("NULL ray or hit array."); }
     else if (!rays || !surfaces || (!hits && !trace)) fail(shade ? "NULL ray, hit or material array." : "NULL ray, hit or surface array.");
+    if (visibility && (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING)) fail("unknown flags (a visibility query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // K3
     if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RAY_FLAG_ACCEPT_FIRST_HIT)) fail("unknown flags.");
     if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surfaces)) & 15u))
-        fail(shade ? "the ray, hit and material arrays must be 16-byte aligned." : resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
+        fail(visibility ? "the ray and visibility arrays must be 16-byte aligned." : shade ? "the ray, hit and material arrays must be 16-byte aligned." : resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
     if (!hostArrays && (reinterpret_cast<uintptr_t>(lods) & 3u)) fail("the lod array must be 4-byte aligned.");
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
@@ -2191,7 +2196,7 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     if (!q.valid) fail("the view has no frame to query (draw one first).");
     if (q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
     for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
-    if (shade && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
+    if ((shade || alpha || visibility) && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
     dev->use();
     query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
     if (count == 0) return;
@@ -2200,7 +2205,7 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     FrameParams P = q.P;
     P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
     P.tileTiming = nullptr; P.traversalStack = nullptr;
-    if (trace && q.needSpill) {         // the walk can outgrow its LDS entries: the query's own slab, sized for its launch
+    if (walk && q.needSpill) {         // the walk can outgrow its LDS entries: the query's own slab, sized for its launch
         const size_t words = ray_query_spill_bytes() / sizeof(uint32_t);
         if (dev->querySlab.count < words) {
             dev->querySlab.reserve(words);
@@ -2214,13 +2219,21 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     if (s != dev->stream) { HIP_CHECK(hipEventRecord(dev->queryOrder, dev->stream)); HIP_CHECK(hipStreamWaitEvent(s, dev->queryOrder, 0)); }
     if (P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slab
     FrameParams R = P; R.traversalStack = nullptr;                    // the resolve reads the instance table and what it points to: no stack, no slab
+    // the walk of the call, if it has one, on device arrays: rays (+ lods) -> RT64_RAY_HITs, or 16-byte RT64_RAY_VISIBILITYs, in `out`
+    auto launch_walk = [&](const void *r, const void *l, void *out, size_t n) {
+        if (visibility) HIP_CHECK(launch_visibility_query(P, r, out, n, flags, s));
+        else if (alpha) HIP_CHECK(launch_alpha_query(P, r, l, out, n, flags, s));
+        else HIP_CHECK(launch_ray_query(P, r, out, n, flags, s));
+    };
     if (hostArrays) {
-        // One round trip per chunk: [rays | hits] up as far as the call brings them, the kernels back to back, [hits | surfaces] down as far as the call wants them.
+        // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | surfaces] down as far as the call wants them.
+        // A walk's records (`hits`: RT64_RAY_HITs, or RT64_RAY_VISIBILITYs from their own device buffer) are made on the device and only come down.
         static_assert(sizeof(RT64_RAY_MATERIAL) == sizeof(RT64_RAY_SURFACE), "one record size for both kinds of resolve");
-        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE), lodB = lods ? sizeof(float) : 0;
-        const size_t upB = rayB + (trace ? 0 : hitB) + lodB, downB = ((trace && hits) ? hitB : 0) + (resolve ? surfB : 0);
+        const size_t rayB = sizeof(RT64_RAY), hitB = visibility ? sizeof(RT64_RAY_VISIBILITY) : sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE), lodB = lods ? sizeof(float) : 0;
+        const size_t upB = rayB + (walk ? 0 : hitB) + lodB, downB = ((walk && hits) ? hitB : 0) + (resolve ? surfB : 0);
         const size_t chunk = std::min<size_t>(count, (size_t)1 << (resolve ? 18 : 20));
-        dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB);
+        DevArray<uint8_t> &walked = visibility ? dev->queryVisibility : dev->queryHits;
+        dev->queryRays.reserve(chunk * rayB); walked.reserve(chunk * hitB);
         DevArray<uint8_t> &records = shade ? dev->queryMaterials : dev->querySurfaces;
         if (resolve) records.reserve(chunk * surfB);
         if (lods) dev->queryLods.reserve(chunk * lodB);
@@ -2229,27 +2242,27 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
             const size_t n = std::min(chunk, count - at);
             memcpy(pin, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
             HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, pin, n * rayB, hipMemcpyHostToDevice, s));
-            if (!trace) {
+            if (!walk) {
                 memcpy(pin + n * rayB, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, pin + n * rayB, n * hitB, hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(walked.ptr, pin + n * rayB, n * hitB, hipMemcpyHostToDevice, s));
             }
             if (lods) {
                 uint8_t *at4 = pin + n * (upB - lodB);
                 memcpy(at4, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
                 HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, at4, n * lodB, hipMemcpyHostToDevice, s));
             }
-            if (trace) HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
+            if (walk) launch_walk(dev->queryRays.ptr, lods ? dev->queryLods.ptr : nullptr, walked.ptr, n);
             if (shade) HIP_CHECK(launch_hit_material(R, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
             else if (resolve) HIP_CHECK(launch_hit_surface(R, dev->queryRays.ptr, dev->queryHits.ptr, records.ptr, n, s));
             uint8_t *down = pin;
-            if (trace && hits) { HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
+            if (walk && hits) { HIP_CHECK(hipMemcpyAsync(down, walked.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
             if (resolve) HIP_CHECK(hipMemcpyAsync(down, records.ptr, n * surfB, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
-            if (trace && hits) memcpy(static_cast<uint8_t *>(hits) + at * hitB, pin, n * hitB);
+            if (walk && hits) memcpy(static_cast<uint8_t *>(hits) + at * hitB, pin, n * hitB);
             if (resolve) memcpy(static_cast<uint8_t *>(surfaces) + at * surfB, down, n * surfB);
         }
     }
-    else if (trace) HIP_CHECK(launch_ray_query(P, rays, hits, count, flags, s));
+    else if (walk) launch_walk(rays, lods, hits, count);
     else if (shade) HIP_CHECK(launch_hit_material(R, rays, hits, lods, surfaces, count, s));
     else HIP_CHECK(launch_hit_surface(R, rays, hits, surfaces, count, s));
     if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
@@ -2441,6 +2454,19 @@ RT64_EXPORT int RT64_TraceViewRayMaterials(RT64_VIEW *view, const RT64_RAY *rays
 RT64_EXPORT int RT64_TraceViewRaySurfaces(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, RT64_RAY_SURFACE *surfaces, size_t count, unsigned int flags) {
     RT64_TRY run_view_query("RT64_TraceViewRaySurfaces", reinterpret_cast<View *>(view), rays, hits, surfaces, count, flags, nullptr, true, QUERY_TRACE | QUERY_RESOLVE); return 1; RT64_CATCH(0)
 }
+RT64_EXPORT int RT64_TraceViewRaysAlpha(RT64_VIEW *view, const RT64_RAY *rays, const float *lods, RT64_RAY_HIT *hits, size_t count, unsigned int flags) {
+    RT64_TRY run_view_query("RT64_TraceViewRaysAlpha", reinterpret_cast<View *>(view), rays, hits, nullptr, count, flags, nullptr, true, QUERY_ALPHA, lods); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRaysAlphaDevice(RT64_VIEW *view, const void *rays, const void *lods, void *hits, size_t count, unsigned int flags, void *stream) {
+    RT64_TRY run_view_query("RT64_TraceViewRaysAlphaDevice", reinterpret_cast<View *>(view), rays, hits, nullptr, count, flags, stream, false, QUERY_ALPHA, lods); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayVisibility(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_VISIBILITY *visibility, size_t count, unsigned int flags) {
+    RT64_TRY run_view_query("RT64_TraceViewRayVisibility", reinterpret_cast<View *>(view), rays, visibility, nullptr, count, flags, nullptr, true, QUERY_VISIBILITY); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayVisibilityDevice(RT64_VIEW *view, const void *rays, void *visibility, size_t count, unsigned int flags, void *stream) {
+    RT64_TRY run_view_query("RT64_TraceViewRayVisibilityDevice", reinterpret_cast<View *>(view), rays, visibility, nullptr, count, flags, stream, false, QUERY_VISIBILITY); return 1; RT64_CATCH(0)
+}
+
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {
     const View *v = reinterpret_cast<View *>(viewPtr);
     if (!v || !v->query.valid || instance < 0 || (size_t)instance >= v->query.instances.size()) return nullptr;

@@ -243,6 +243,14 @@ MATERIAL_API = [
 ]
 (MATERIAL_VALID, MATERIAL_BAD_HIT, MATERIAL_TEXTURED, MATERIAL_NORMAL_MAPPED, MATERIAL_SPECULAR_MAPPED, MATERIAL_CUTOUT, MATERIAL_SHADOW_CUTOUT,
  MATERIAL_NOISE_ALPHA, MATERIAL_BACK_FACE) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x100
+# include/rt64_alpha.h: walks that honour alpha (rules K1-K10), a list and a loader (RT64_LoadLibraryAlpha) of its own
+ALPHA_API = [
+    ("TraceViewRaysAlpha", "RT64_TraceViewRaysAlpha", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint]),
+    ("TraceViewRaysAlphaDevice", "RT64_TraceViewRaysAlphaDevice", C.c_int, [_P, _P, _P, _P, C.c_size_t, C.c_uint, _P]),
+    ("TraceViewRayVisibility", "RT64_TraceViewRayVisibility", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint]),
+    ("TraceViewRayVisibilityDevice", "RT64_TraceViewRayVisibilityDevice", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P]),
+]
+VISIBILITY_VALID, VISIBILITY_BLOCKED = 0x1, 0x2
 
 
 class RAY(C.Structure):
@@ -264,6 +272,11 @@ class RAY_MATERIAL(C.Structure):
                 ("lod", C.c_float), ("instance", C.c_int), ("primitive", C.c_uint), ("reserved", C.c_uint)]
 
 
+class RAY_VISIBILITY(C.Structure):
+    _fields_ = [("visibility", C.c_float), ("flags", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
+
+
+assert C.sizeof(RAY_VISIBILITY) == 16
 assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
 
 HALO_ROWS = 62
@@ -289,7 +302,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -428,3 +441,64 @@ def trace_materials(lib, view, rays, lods=None, flags=0):
     if not lib.TraceViewRayMaterials(view, rays.ctypes.data, hits.ctypes.data, lods.ctypes.data if lods is not None else None, out.ctypes.data, rays.shape[0], flags):
         raise RuntimeError(lib.last_error())
     return hits, out
+
+
+def trace_rays_alpha(lib, view, rays, lods=None, flags=0, stream=None):
+    """RT64_TraceViewRaysAlpha: (N, 8) float32 rays and, optionally, (N,) float32 lods (None: level 0 for every ray) -> (N, 8) float32 hits as
+    trace_rays returns them, the closest intersection a texture-edge shader does not cut out (rule K2).  NumPy arrays take the host path; torch
+    CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    if type(rays).__module__.split(".")[0] == "torch":
+        import torch
+        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_cuda:
+            raise ValueError("rays: an (N, 8) float32 CUDA tensor")
+        if lods is not None:
+            if lods.dim() != 1 or lods.shape[0] != rays.shape[0] or lods.dtype != torch.float32 or not lods.is_cuda:
+                raise ValueError("lods: an (N,) float32 CUDA tensor")
+            lods = lods.contiguous()
+        rays = rays.contiguous()
+        hits = torch.empty_like(rays)
+        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+        if s != torch.cuda.current_stream(rays.device):
+            for a in (rays, hits) + ((lods,) if lods is not None else ()):
+                a.record_stream(s)
+        ok = lib.TraceViewRaysAlphaDevice(view, rays.data_ptr(), lods.data_ptr() if lods is not None else None, hits.data_ptr(), rays.shape[0], flags, s.cuda_stream)
+    else:
+        import numpy as np
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: an (N, 8) float32 array")
+        if lods is not None:
+            lods = np.ascontiguousarray(lods, dtype=np.float32)
+            if lods.shape != (rays.shape[0],):
+                raise ValueError("lods: an (N,) float32 array")
+        hits = np.empty_like(rays)
+        ok = lib.TraceViewRaysAlpha(view, rays.ctypes.data, lods.ctypes.data if lods is not None else None, hits.ctypes.data, rays.shape[0], flags)
+    if not ok:
+        raise RuntimeError(lib.last_error())
+    return hits
+
+
+def trace_visibility(lib, view, rays, flags=0, stream=None):
+    """RT64_TraceViewRayVisibility: (N, 8) float32 rays -> (N, 4) float32 RT64_RAY_VISIBILITYs: visibility, then flags, nodesVisited, trianglesTested
+    as uint32 bits (read them through `.view(int32)`): what a frame's shadow ray returns for the ray, noise aside (rule K5).  NumPy arrays take the
+    host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    if type(rays).__module__.split(".")[0] == "torch":
+        import torch
+        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_cuda:
+            raise ValueError("rays: an (N, 8) float32 CUDA tensor")
+        rays = rays.contiguous()
+        out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
+        if s != torch.cuda.current_stream(rays.device):
+            rays.record_stream(s); out.record_stream(s)
+        ok = lib.TraceViewRayVisibilityDevice(view, rays.data_ptr(), out.data_ptr(), rays.shape[0], flags, s.cuda_stream)
+    else:
+        import numpy as np
+        rays = np.ascontiguousarray(rays, dtype=np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError("rays: an (N, 8) float32 array")
+        out = np.empty((rays.shape[0], 4), dtype=np.float32)
+        ok = lib.TraceViewRayVisibility(view, rays.ctypes.data, out.ctypes.data, rays.shape[0], flags)
+    if not ok:
+        raise RuntimeError(lib.last_error())
+    return out
