@@ -1,7 +1,7 @@
 // material.hip -- material records for the hits of a ray query (RT64_ShadeViewRayHits, include/rt64_material.h; rules H1-H12 in DESIGN.md 4).
 //
-// A streaming kernel beside hit_surface_kernel, not part of the walk: one hit per lane, RT_BLOCK threads per workgroup, at most RT_GRID_BLOCKS workgroups that
-// stride over the records in the order given.  Per record it reads 64 bytes (ray + hit, 16-byte loads) and one optional float (the lod), follows
+// A resolve kernel of query_common.h beside hit_surface_kernel, not part of the walk.  Per record it reads 64 bytes (ray + hit, 16-byte loads) and one optional
+// float (the lod), follows
 // indices[3 prim + k] to three vertices, samples up to three textures and writes 64 bytes (four 16-byte stores).  No LDS, no traversal stack, no spill slab.
 // The arithmetic is inst_view, get_vertex_data, color_formula, alpha_formula and tex_sample_level of shade.h -- the functions the frame's any-hit programs
 // (surface_anyhit_view, shadow_anyhit_alpha_view) run, in their order -- so colour, normal, specular and shadow alpha are the frame's own before quantisation,
@@ -10,27 +10,12 @@
 // The instance differs per lane and, unlike in surface.hip, steers control flow (combiner shape, filter, addressing, map flags).  A wave whose hits all lie on
 // one instance reads that instance's record into scalar registers and branches uniformly; any other wave has every lane gather its own instance record with
 // vector loads (the surface.hip scheme; DESIGN.md 4 has the figures against the any-hit's `waterfall`).
-#include "kernels.h"
-#include "shade.h"
+#include "query_common.h"
+#include "alpha.h"
 
 namespace {
 
 struct MaterialRecord { f4 color; f3 shadingNormal, specular; float shadowAlpha, lod; uint32_t flags; };
-
-// H3: the tail of tex_sample_grad behind its log2 -- clamp, then one level (POINT) or two blended (LINEAR).  `clamped` is the lod the sample was taken at.
-DEV f4 tex_sample_lod(const TexView &t, float u, float v, float lod, uint32_t filter, uint32_t hAddr, uint32_t vAddr, float &clamped) {
-    clamped = 0.0f;
-    if (t.mips == 1) return tex_sample_level(t, u, v, 0, filter, hAddr, vAddr);
-    const float maxLod = (float)(t.mips - 1);
-    if (!(lod > 0.0f)) lod = 0.0f;                       // (NaN as well)
-    if (lod > maxLod) lod = maxLod;
-    clamped = lod;
-    if (filter == 0) return tex_sample_level(t, u, v, (uint32_t)(int)(lod + 0.5f), filter, hAddr, vAddr);
-    int l0 = (int)floorf(lod), l1 = l0 + 1 < (int)t.mips ? l0 + 1 : (int)t.mips - 1;
-    float f = lod - (float)l0;
-    f4 a = tex_sample_level(t, u, v, (uint32_t)l0, filter, hAddr, vAddr), b = tex_sample_level(t, u, v, (uint32_t)l1, filter, hAddr, vAddr);
-    return mk4(a.x + f * (b.x - a.x), a.y + f * (b.y - a.y), a.z + f * (b.z - a.z), a.w + f * (b.w - a.w));
-}
 
 // H2-H10 for one real hit of instance `in`: the body of surface_anyhit_view without pixel, frame number and quantisation, then shadow_anyhit_alpha_view's on the same vertex data
 DEV void material_of_hit(PRef P, const InstView &in, uint32_t prim, float u, float v, f3 rayDirW, float lod, MaterialRecord &r) {
@@ -54,7 +39,8 @@ DEV void material_of_hit(PRef P, const InstView &in, uint32_t prim, float u, flo
         t0s = tex_sample_level(tv, vd.vertexUV.x, vd.vertexUV.y, 0, in.filter, in.hAddr, in.vAddr);
         r.flags |= RT64_MATERIAL_TEXTURED;
     }
-    f4 result; float sa;                                                                    // H5
+    // H5, written out: result.w and sa are combiner_alpha(cc, vd, t0 / t0s) of alpha.h -- the same calls -- but taken from there the kernel compiles to other machine code
+    f4 result; float sa;
     if (!cc.colorAlphaSame && cc.optAlpha) {
         result = color_formula(cc, false, true, vd, t0, t1);
         result.w = alpha_formula(cc, vd, t0, t1);
@@ -71,8 +57,8 @@ DEV void material_of_hit(PRef P, const InstView &in, uint32_t prim, float u, flo
     result.w = clampf(mat.solidAlphaMultiplier * result.w, 0.0f, 1.0f);
     sa = clampf(sa * mat.shadowAlphaMultiplier, 0.0f, 1.0f);                                // H10
     if (cc.optTextureEdge) {                                                                // H6
-        if (result.w > 0.3f) result.w = 1.0f; else r.flags |= RT64_MATERIAL_CUTOUT;
-        if (sa > 0.3f) sa = 1.0f; else r.flags |= RT64_MATERIAL_SHADOW_CUTOUT;
+        if (result.w > RT64_EDGE_ALPHA) result.w = 1.0f; else r.flags |= RT64_MATERIAL_CUTOUT;
+        if (sa > RT64_EDGE_ALPHA) sa = 1.0f; else r.flags |= RT64_MATERIAL_SHADOW_CUTOUT;
     }
     if (cc.optNoise) r.flags |= RT64_MATERIAL_NOISE_ALPHA;                                  // H7
     r.color = result; r.shadowAlpha = sa;
@@ -104,17 +90,15 @@ DEV void material_of_hit(PRef P, const InstView &in, uint32_t prim, float u, flo
 
 __global__ __launch_bounds__(RT_BLOCK) void hit_material_kernel(FrameParams Pv, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, RT64_RAY_MATERIAL *materials, uint64_t count) {
     PRef P = *kernel_params(); (void)Pv;
-    typedef const u32x4 __attribute__((address_space(1))) *GIn;
-    typedef u32x4 __attribute__((address_space(1))) *GOut;
-    const uint64_t stride = (uint64_t)gridDim.x * RT_BLOCK;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_BLOCK + threadIdx.x; i < count; i += stride) {
-        GIn rsrc = reinterpret_cast<GIn>(reinterpret_cast<uintptr_t>(rays + i)), hsrc = reinterpret_cast<GIn>(reinterpret_cast<uintptr_t>(hits + i));
-        const u32x4 rb = rsrc[1];                       // direction + tMax (a record does not depend on the origin)
-        const u32x4 h0 = hsrc[0], h1 = hsrc[1];         // t, u, v, instance / primitive, counters
+    const uint64_t stride = query_stride();
+    for (uint64_t i = query_first(); i < count; i += stride) {
+        const GIn rsrc = QUERY_IN(rays + i), hsrc = QUERY_IN(hits + i);
+        const QueryRay ray = load_ray(rsrc);          // (a record does not depend on the origin: that load is dead code)
+        const QueryHit h = load_hit(hsrc);
         const float lod = lods ? lods[i] : 0.0f;
-        const f3 dir = mk3(__uint_as_float(rb.x), __uint_as_float(rb.y), __uint_as_float(rb.z));
-        const float u = __uint_as_float(h0.y), v = __uint_as_float(h0.z);
-        const uint32_t instance = h0.w, prim = h1.x;
+        const f3 dir = mk3(ray.d[0], ray.d[1], ray.d[2]);
+        const uint32_t instance = h.instance, prim = h.prim;
+        const float u = h.u, v = h.v;
         // H1: the miss record; nothing below reads through an index that is out of range
         MaterialRecord r;
         r.color = mk4(0, 0, 0, 0); r.shadingNormal = r.specular = mk3s(0.0f); r.shadowAlpha = r.lod = 0.0f;
@@ -132,7 +116,7 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_material_kernel(FrameParams Pv, 
         o1.x = __float_as_uint(r.shadingNormal.x); o1.y = __float_as_uint(r.shadingNormal.y); o1.z = __float_as_uint(r.shadingNormal.z); o1.w = r.flags;
         o2.x = __float_as_uint(r.specular.x); o2.y = __float_as_uint(r.specular.y); o2.z = __float_as_uint(r.specular.z); o2.w = __float_as_uint(r.shadowAlpha);
         o3.x = __float_as_uint(r.lod); o3.y = real ? instance : 0xFFFFFFFFu; o3.z = real ? prim : 0xFFFFFFFFu; o3.w = 0u;
-        GOut dst = reinterpret_cast<GOut>(reinterpret_cast<uintptr_t>(materials + i));
+        GOut dst = QUERY_OUT(materials + i);
         dst[0] = o0; dst[1] = o1; dst[2] = o2; dst[3] = o3;
     }
 }
@@ -141,9 +125,7 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_material_kernel(FrameParams Pv, 
 
 hipError_t launch_hit_material(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *materials, uint64_t count, hipStream_t s) {
     if (!count) return hipSuccess;
-    const uint64_t blocks = (count + RT_BLOCK - 1) / RT_BLOCK;
-    const dim3 grid((unsigned)(blocks < RT_GRID_BLOCKS ? blocks : RT_GRID_BLOCKS)), block(RT_BLOCK);
-    hipLaunchKernelGGL(hit_material_kernel, grid, block, 0, s, P, static_cast<const RT64_RAY *>(rays), static_cast<const RT64_RAY_HIT *>(hits),
+    hipLaunchKernelGGL(hit_material_kernel, query_grid(count), dim3(RT_BLOCK), 0, s, P, static_cast<const RT64_RAY *>(rays), static_cast<const RT64_RAY_HIT *>(hits),
                        static_cast<const float *>(lods), static_cast<RT64_RAY_MATERIAL *>(materials), count);
     return hipGetLastError();
 }

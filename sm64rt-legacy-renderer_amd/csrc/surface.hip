@@ -1,7 +1,6 @@
 // surface.hip -- surface records for the hits of a ray query (RT64_ResolveViewRayHits, include/rt64_surface.h; rules A1-A9 in DESIGN.md 4).
 //
-// A streaming kernel beside the walk, not part of it: one hit per lane, RT_BLOCK threads per workgroup, at most RT_GRID_BLOCKS workgroups that stride over
-// the records in the order given.  Per record it reads 64 bytes (ray + hit, 16-byte loads), follows indices[3 prim + k] to three vertices, and writes 64 bytes
+// A resolve kernel of query_common.h: a streaming kernel beside the walk, not part of it.  Per record it reads 64 bytes (ray + hit, 16-byte loads), follows indices[3 prim + k] to three vertices, and writes 64 bytes
 // (four 16-byte stores).  No LDS, no traversal stack, no spill slab.  The arithmetic is inst_view + get_vertex_data of shade.h -- the functions the frame's
 // any-hit program (surface_anyhit_view) runs -- so position, normals and UV are the frame's own, before normal mapping and before quantisation; the loads of
 // the InstView / VertexData fields a record does not use (material, previous transform, combiner inputs, texture slots) are dead code and not emitted.
@@ -9,9 +8,9 @@
 // The instance differs per lane.  A wave whose hits all lie on one instance (coherent rays: most waves of a camera-like batch) reads that instance's two
 // matrices, array pointers, vertex layout and triangle count into scalar registers; any other wave has every lane gather its own instance record (some 40
 // dwords) with vector loads.  The any-hit's `waterfall` -- one scalar pass per distinct instance -- was measured as well: equal on coherent waves, 2.1 x
-// slower on a shuffled batch over 66 instances.
-#include "kernels.h"
-#include "shade.h"
+// slower on a shuffled batch over 66 instances.  hit_material_kernel repeats this block: behind a shared dispatcher (a function taking the
+// per-hit code) both kernels compiled to other machine code, and this one ran 0.5 % slower on shuffled rays over 66 instances, so the block stays in the kernels.
+#include "query_common.h"
 
 namespace {
 
@@ -34,16 +33,13 @@ DEV void surface_of_hit(const InstView &in, uint32_t prim, float u, float v, f3 
 
 __global__ __launch_bounds__(RT_BLOCK) void hit_surface_kernel(FrameParams Pv, const RT64_RAY *rays, const RT64_RAY_HIT *hits, RT64_RAY_SURFACE *surfaces, uint64_t count) {
     PRef P = *kernel_params(); (void)Pv;
-    typedef const u32x4 __attribute__((address_space(1))) *GIn;
-    typedef u32x4 __attribute__((address_space(1))) *GOut;
-    const uint64_t stride = (uint64_t)gridDim.x * RT_BLOCK;
-    for (uint64_t i = (uint64_t)blockIdx.x * RT_BLOCK + threadIdx.x; i < count; i += stride) {
-        GIn rsrc = reinterpret_cast<GIn>(reinterpret_cast<uintptr_t>(rays + i)), hsrc = reinterpret_cast<GIn>(reinterpret_cast<uintptr_t>(hits + i));
-        const u32x4 rb = rsrc[1];                       // direction + tMax (a record does not depend on the origin)
-        const u32x4 h0 = hsrc[0], h1 = hsrc[1];         // t, u, v, instance / primitive, counters
-        const f3 dir = mk3(__uint_as_float(rb.x), __uint_as_float(rb.y), __uint_as_float(rb.z));
-        const float u = __uint_as_float(h0.y), v = __uint_as_float(h0.z);
-        const uint32_t instance = h0.w, prim = h1.x;
+    const uint64_t stride = query_stride();
+    for (uint64_t i = query_first(); i < count; i += stride) {
+        const QueryRay ray = load_ray(QUERY_IN(rays + i));          // (a record does not depend on the origin: that load is dead code)
+        const QueryHit h = load_hit(QUERY_IN(hits + i));
+        const f3 dir = mk3(ray.d[0], ray.d[1], ray.d[2]);
+        const uint32_t instance = h.instance, prim = h.prim;
+        const float u = h.u, v = h.v;
         // A2 / A3: the miss record; nothing below reads through an index that is out of range
         SurfaceRecord r;
         r.position = r.geometricNormal = r.shadingNormal = mk3s(0.0f); r.uv.x = r.uv.y = 0.0f;
@@ -60,8 +56,8 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_surface_kernel(FrameParams Pv, c
         o0.x = __float_as_uint(r.position.x); o0.y = __float_as_uint(r.position.y); o0.z = __float_as_uint(r.position.z); o0.w = r.flags;
         o1.x = __float_as_uint(r.geometricNormal.x); o1.y = __float_as_uint(r.geometricNormal.y); o1.z = __float_as_uint(r.geometricNormal.z); o1.w = real ? instance : 0xFFFFFFFFu;
         o2.x = __float_as_uint(r.shadingNormal.x); o2.y = __float_as_uint(r.shadingNormal.y); o2.z = __float_as_uint(r.shadingNormal.z); o2.w = real ? prim : 0xFFFFFFFFu;
-        o3.x = __float_as_uint(r.uv.x); o3.y = __float_as_uint(r.uv.y); o3.z = real ? h0.x : __float_as_uint(INFINITY); o3.w = 0u;
-        GOut dst = reinterpret_cast<GOut>(reinterpret_cast<uintptr_t>(surfaces + i));
+        o3.x = __float_as_uint(r.uv.x); o3.y = __float_as_uint(r.uv.y); o3.z = real ? __float_as_uint(h.t) : __float_as_uint(INFINITY); o3.w = 0u;
+        GOut dst = QUERY_OUT(surfaces + i);
         dst[0] = o0; dst[1] = o1; dst[2] = o2; dst[3] = o3;
     }
 }
@@ -70,9 +66,7 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_surface_kernel(FrameParams Pv, c
 
 hipError_t launch_hit_surface(const FrameParams &P, const void *rays, const void *hits, void *surfaces, uint64_t count, hipStream_t s) {
     if (!count) return hipSuccess;
-    const uint64_t blocks = (count + RT_BLOCK - 1) / RT_BLOCK;
-    const dim3 grid((unsigned)(blocks < RT_GRID_BLOCKS ? blocks : RT_GRID_BLOCKS)), block(RT_BLOCK);
-    hipLaunchKernelGGL(hit_surface_kernel, grid, block, 0, s, P, static_cast<const RT64_RAY *>(rays), static_cast<const RT64_RAY_HIT *>(hits),
+    hipLaunchKernelGGL(hit_surface_kernel, query_grid(count), dim3(RT_BLOCK), 0, s, P, static_cast<const RT64_RAY *>(rays), static_cast<const RT64_RAY_HIT *>(hits),
                        static_cast<RT64_RAY_SURFACE *>(surfaces), count);
     return hipGetLastError();
 }

@@ -318,73 +318,74 @@ def exported_symbols():
     return [s for _, s, _, _ in API + EXT_API]
 
 
+def _query(lib, view, host, device, args, flags=None, stream=None):
+    """The call behind every ray-query wrapper.  `args` lists the entry point's array arguments in its order as (kind, value) pairs: ("in", an (N, 8)
+    float32 array: rays, hits), ("lods", an (N,) float32 array, or None for NULL), ("out", the width of an (N, width) float32 array to allocate).
+    NumPy inputs go to the entry point `host`; torch tensors to `device` (None: the call has no device form), enqueued on `stream`.  Behind the
+    arrays go count, flags (unless None) and the stream.  Returns the outputs in order; raises ValueError for a wrong array,
+    RuntimeError(RT64_GetLastError) on a refusal."""
+    ins = [v for kind, v in args if kind == "in"]
+    lods = next((v for kind, v in args if kind == "lods"), None)
+    on_device = device is not None and type(ins[0]).__module__.split(".")[0] == "torch"
+    if on_device:
+        import torch
+        for a in ins:
+            if a.dim() != 2 or a.shape[1] != 8 or a.dtype != torch.float32 or not a.is_cuda:
+                raise ValueError("rays: an (N, 8) float32 CUDA tensor" if len(ins) == 1 else "rays, hits: (N, 8) float32 CUDA tensors")
+        if any(a.shape[0] != ins[0].shape[0] for a in ins):
+            raise ValueError("one hit per ray")
+        if lods is not None and (lods.dim() != 1 or lods.shape[0] != ins[0].shape[0] or lods.dtype != torch.float32 or not lods.is_cuda):
+            raise ValueError("lods: an (N,) float32 CUDA tensor")
+        ins, lods = [a.contiguous() for a in ins], lods.contiguous() if lods is not None else None
+        new = lambda width: torch.empty((ins[0].shape[0], width), dtype=torch.float32, device=ins[0].device)
+        address = lambda a: a.data_ptr()
+    else:
+        import numpy as np
+        ins = [np.ascontiguousarray(a, dtype=np.float32) for a in ins]
+        if ins[0].ndim != 2 or ins[0].shape[1] != 8 or any(a.shape != ins[0].shape for a in ins):
+            raise ValueError("rays: an (N, 8) float32 array" if len(ins) == 1 else "rays, hits: (N, 8) float32 arrays of one length")
+        if lods is not None:
+            lods = np.ascontiguousarray(lods, dtype=np.float32)
+            if lods.shape != (ins[0].shape[0],):
+                raise ValueError("lods: an (N,) float32 array")
+        new = lambda width: np.empty((ins[0].shape[0], width), dtype=np.float32)
+        address = lambda a: a.ctypes.data
+    checked = iter(ins)
+    arrays = [next(checked) if kind == "in" else lods if kind == "lods" else new(v) for kind, v in args]          # the entry point's arrays, in its order
+    outs = [a for (kind, _), a in zip(args, arrays) if kind == "out"]
+    tail = []
+    if on_device:
+        s = stream if stream is not None else torch.cuda.current_stream(ins[0].device)
+        if s != torch.cuda.current_stream(ins[0].device):
+            for a in arrays:          # (the allocator must not hand the memory out again before the query has run)
+                if a is not None:
+                    a.record_stream(s)
+        tail = [s.cuda_stream]
+    pointers = [address(a) if a is not None else None for a in arrays]
+    if not getattr(lib, device if on_device else host)(view, *pointers, ins[0].shape[0], *([] if flags is None else [flags]), *tail):
+        raise RuntimeError(lib.last_error())
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
 def trace_rays(lib, view, rays, flags=0, stream=None):
     """RT64_TraceViewRays on an (N, 8) float32 array of RT64_RAYs: origin xyz, tMin, direction xyz, tMax.
 
     A NumPy array takes the host path; a torch CUDA tensor the device path, enqueued on `stream` (a torch stream; default the tensor's
     current stream) behind the view's last frame.  Returns (N, 8) float32 hits of the same kind -- t, u, v, then instance, primitive,
     nodesVisited, trianglesTested, reserved as int32 / uint32 bits (read them through `.view(int32)`).  Raises with RT64_GetLastError on a refusal."""
-    if type(rays).__module__.split(".")[0] == "torch":
-        import torch
-        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_cuda:
-            raise ValueError("rays: an (N, 8) float32 CUDA tensor")
-        rays = rays.contiguous()
-        hits = torch.empty_like(rays)
-        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-        if s != torch.cuda.current_stream(rays.device):
-            rays.record_stream(s); hits.record_stream(s)      # (the allocator must not hand the memory out again before the query has run)
-        ok = lib.TraceViewRaysDevice(view, rays.data_ptr(), hits.data_ptr(), rays.shape[0], flags, s.cuda_stream)
-    else:
-        import numpy as np
-        rays = np.ascontiguousarray(rays, dtype=np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError("rays: an (N, 8) float32 array")
-        hits = np.empty_like(rays)
-        ok = lib.TraceViewRays(view, rays.ctypes.data, hits.ctypes.data, rays.shape[0], flags)
-    if not ok:
-        raise RuntimeError(lib.last_error())
-    return hits
+    return _query(lib, view, "TraceViewRays", "TraceViewRaysDevice", [("in", rays), ("out", 8)], flags, stream)
 
 
 def resolve_hits(lib, view, rays, hits, stream=None):
     """RT64_ResolveViewRayHits: (N, 8) float32 rays and the (N, 8) float32 hits trace_rays returned for them -> (N, 16) float32 RT64_RAY_SURFACEs:
     position xyz, flags, geometricNormal xyz, instance, shadingNormal xyz, primitive, uv, t, reserved (flags, instance, primitive as uint32 / int32
     bits: read them through `.view(int32)`).  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
-    if type(rays).__module__.split(".")[0] == "torch":
-        import torch
-        for a in (rays, hits):
-            if a.dim() != 2 or a.shape[1] != 8 or a.dtype != torch.float32 or not a.is_cuda:
-                raise ValueError("rays, hits: (N, 8) float32 CUDA tensors")
-        if rays.shape[0] != hits.shape[0]:
-            raise ValueError("one hit per ray")
-        rays, hits = rays.contiguous(), hits.contiguous()
-        out = torch.empty((rays.shape[0], 16), dtype=torch.float32, device=rays.device)
-        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-        if s != torch.cuda.current_stream(rays.device):
-            rays.record_stream(s); hits.record_stream(s); out.record_stream(s)
-        ok = lib.ResolveViewRayHitsDevice(view, rays.data_ptr(), hits.data_ptr(), out.data_ptr(), rays.shape[0], s.cuda_stream)
-    else:
-        import numpy as np
-        rays, hits = np.ascontiguousarray(rays, dtype=np.float32), np.ascontiguousarray(hits, dtype=np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != rays.shape:
-            raise ValueError("rays, hits: (N, 8) float32 arrays of one length")
-        out = np.empty((rays.shape[0], 16), dtype=np.float32)
-        ok = lib.ResolveViewRayHits(view, rays.ctypes.data, hits.ctypes.data, out.ctypes.data, rays.shape[0])
-    if not ok:
-        raise RuntimeError(lib.last_error())
-    return out
+    return _query(lib, view, "ResolveViewRayHits", "ResolveViewRayHitsDevice", [("in", rays), ("in", hits), ("out", 16)], None, stream)
 
 
 def trace_surfaces(lib, view, rays, flags=0):
     """RT64_TraceViewRaySurfaces on an (N, 8) float32 NumPy array of rays: trace and resolve in one staging round trip -> (hits (N, 8), surfaces (N, 16))."""
-    import numpy as np
-    rays = np.ascontiguousarray(rays, dtype=np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("rays: an (N, 8) float32 array")
-    hits, out = np.empty_like(rays), np.empty((rays.shape[0], 16), dtype=np.float32)
-    if not lib.TraceViewRaySurfaces(view, rays.ctypes.data, hits.ctypes.data, out.ctypes.data, rays.shape[0], flags):
-        raise RuntimeError(lib.last_error())
-    return hits, out
+    return _query(lib, view, "TraceViewRaySurfaces", None, [("in", rays), ("out", 8), ("out", 16)], flags)
 
 
 def shade_hits(lib, view, rays, hits, lods=None, stream=None):
@@ -392,113 +393,24 @@ def shade_hits(lib, view, rays, hits, lods=None, stream=None):
     (None: level 0 for every record) -> (N, 16) float32 RT64_RAY_MATERIALs: color rgba, shadingNormal xyz, flags, specular xyz, shadowAlpha,
     lod, instance, primitive, reserved (flags, instance, primitive as uint32 / int32 bits: read them through `.view(int32)`).  NumPy arrays
     take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
-    if type(rays).__module__.split(".")[0] == "torch":
-        import torch
-        for a in (rays, hits):
-            if a.dim() != 2 or a.shape[1] != 8 or a.dtype != torch.float32 or not a.is_cuda:
-                raise ValueError("rays, hits: (N, 8) float32 CUDA tensors")
-        if rays.shape[0] != hits.shape[0]:
-            raise ValueError("one hit per ray")
-        if lods is not None:
-            if lods.dim() != 1 or lods.shape[0] != rays.shape[0] or lods.dtype != torch.float32 or not lods.is_cuda:
-                raise ValueError("lods: an (N,) float32 CUDA tensor")
-            lods = lods.contiguous()
-        rays, hits = rays.contiguous(), hits.contiguous()
-        out = torch.empty((rays.shape[0], 16), dtype=torch.float32, device=rays.device)
-        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-        if s != torch.cuda.current_stream(rays.device):
-            for a in (rays, hits, out) + ((lods,) if lods is not None else ()):
-                a.record_stream(s)
-        ok = lib.ShadeViewRayHitsDevice(view, rays.data_ptr(), hits.data_ptr(), lods.data_ptr() if lods is not None else None, out.data_ptr(), rays.shape[0], s.cuda_stream)
-    else:
-        import numpy as np
-        rays, hits = np.ascontiguousarray(rays, dtype=np.float32), np.ascontiguousarray(hits, dtype=np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8 or hits.shape != rays.shape:
-            raise ValueError("rays, hits: (N, 8) float32 arrays of one length")
-        if lods is not None:
-            lods = np.ascontiguousarray(lods, dtype=np.float32)
-            if lods.shape != (rays.shape[0],):
-                raise ValueError("lods: an (N,) float32 array")
-        out = np.empty((rays.shape[0], 16), dtype=np.float32)
-        ok = lib.ShadeViewRayHits(view, rays.ctypes.data, hits.ctypes.data, lods.ctypes.data if lods is not None else None, out.ctypes.data, rays.shape[0])
-    if not ok:
-        raise RuntimeError(lib.last_error())
-    return out
+    return _query(lib, view, "ShadeViewRayHits", "ShadeViewRayHitsDevice", [("in", rays), ("in", hits), ("lods", lods), ("out", 16)], None, stream)
 
 
 def trace_materials(lib, view, rays, lods=None, flags=0):
     """RT64_TraceViewRayMaterials on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): trace and shade in one staging
     round trip -> (hits (N, 8), materials (N, 16))."""
-    import numpy as np
-    rays = np.ascontiguousarray(rays, dtype=np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("rays: an (N, 8) float32 array")
-    if lods is not None:
-        lods = np.ascontiguousarray(lods, dtype=np.float32)
-        if lods.shape != (rays.shape[0],):
-            raise ValueError("lods: an (N,) float32 array")
-    hits, out = np.empty_like(rays), np.empty((rays.shape[0], 16), dtype=np.float32)
-    if not lib.TraceViewRayMaterials(view, rays.ctypes.data, hits.ctypes.data, lods.ctypes.data if lods is not None else None, out.ctypes.data, rays.shape[0], flags):
-        raise RuntimeError(lib.last_error())
-    return hits, out
+    return _query(lib, view, "TraceViewRayMaterials", None, [("in", rays), ("out", 8), ("lods", lods), ("out", 16)], flags)
 
 
 def trace_rays_alpha(lib, view, rays, lods=None, flags=0, stream=None):
     """RT64_TraceViewRaysAlpha: (N, 8) float32 rays and, optionally, (N,) float32 lods (None: level 0 for every ray) -> (N, 8) float32 hits as
     trace_rays returns them, the closest intersection a texture-edge shader does not cut out (rule K2).  NumPy arrays take the host path; torch
     CUDA tensors the device path, enqueued on `stream` like trace_rays."""
-    if type(rays).__module__.split(".")[0] == "torch":
-        import torch
-        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_cuda:
-            raise ValueError("rays: an (N, 8) float32 CUDA tensor")
-        if lods is not None:
-            if lods.dim() != 1 or lods.shape[0] != rays.shape[0] or lods.dtype != torch.float32 or not lods.is_cuda:
-                raise ValueError("lods: an (N,) float32 CUDA tensor")
-            lods = lods.contiguous()
-        rays = rays.contiguous()
-        hits = torch.empty_like(rays)
-        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-        if s != torch.cuda.current_stream(rays.device):
-            for a in (rays, hits) + ((lods,) if lods is not None else ()):
-                a.record_stream(s)
-        ok = lib.TraceViewRaysAlphaDevice(view, rays.data_ptr(), lods.data_ptr() if lods is not None else None, hits.data_ptr(), rays.shape[0], flags, s.cuda_stream)
-    else:
-        import numpy as np
-        rays = np.ascontiguousarray(rays, dtype=np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError("rays: an (N, 8) float32 array")
-        if lods is not None:
-            lods = np.ascontiguousarray(lods, dtype=np.float32)
-            if lods.shape != (rays.shape[0],):
-                raise ValueError("lods: an (N,) float32 array")
-        hits = np.empty_like(rays)
-        ok = lib.TraceViewRaysAlpha(view, rays.ctypes.data, lods.ctypes.data if lods is not None else None, hits.ctypes.data, rays.shape[0], flags)
-    if not ok:
-        raise RuntimeError(lib.last_error())
-    return hits
+    return _query(lib, view, "TraceViewRaysAlpha", "TraceViewRaysAlphaDevice", [("in", rays), ("lods", lods), ("out", 8)], flags, stream)
 
 
 def trace_visibility(lib, view, rays, flags=0, stream=None):
     """RT64_TraceViewRayVisibility: (N, 8) float32 rays -> (N, 4) float32 RT64_RAY_VISIBILITYs: visibility, then flags, nodesVisited, trianglesTested
     as uint32 bits (read them through `.view(int32)`): what a frame's shadow ray returns for the ray, noise aside (rule K5).  NumPy arrays take the
     host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
-    if type(rays).__module__.split(".")[0] == "torch":
-        import torch
-        if rays.dim() != 2 or rays.shape[1] != 8 or rays.dtype != torch.float32 or not rays.is_cuda:
-            raise ValueError("rays: an (N, 8) float32 CUDA tensor")
-        rays = rays.contiguous()
-        out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
-        s = stream if stream is not None else torch.cuda.current_stream(rays.device)
-        if s != torch.cuda.current_stream(rays.device):
-            rays.record_stream(s); out.record_stream(s)
-        ok = lib.TraceViewRayVisibilityDevice(view, rays.data_ptr(), out.data_ptr(), rays.shape[0], flags, s.cuda_stream)
-    else:
-        import numpy as np
-        rays = np.ascontiguousarray(rays, dtype=np.float32)
-        if rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError("rays: an (N, 8) float32 array")
-        out = np.empty((rays.shape[0], 4), dtype=np.float32)
-        ok = lib.TraceViewRayVisibility(view, rays.ctypes.data, out.ctypes.data, rays.shape[0], flags)
-    if not ok:
-        raise RuntimeError(lib.last_error())
-    return out
+    return _query(lib, view, "TraceViewRayVisibility", "TraceViewRayVisibilityDevice", [("in", rays), ("out", 4)], flags, stream)

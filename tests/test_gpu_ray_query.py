@@ -92,6 +92,47 @@ def test_large_mesh_rays_match_the_oracle(rt64_lib):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("lds_cache", [1, 0])
+def test_sizes_grid_stride_and_the_end_of_the_array(rt64_lib, sample_data, lds_cache):
+    """Counts 1, 63, 64, 65, 255, 256, 257 and RT_GRID_BLOCKS x RT_BLOCK + 65 (the smallest that makes one lane take a second ray of the grid-stride loop),
+    closest hit and ACCEPT_FIRST_HIT, walked from the LDS scene cache and from HBM: each equals the prefix of one big call, on the device form (258 guard
+    records behind the last one untouched) and, up to 257, on the host form.  Counters included: a ray's record does not depend on its slot or its neighbours."""
+    from sm64rt_legacy_renderer_amd import rt64, sample_scene
+    s = sample_scene.Rt64Scene(rt64_lib, sample_data, W, H, hip_device=0)
+    hip = ray_rule.Hip()
+    try:
+        assert s.option("lds_cache", lds_cache) and s.option("count_traversal", 1)
+        s.draw()
+        rays = ray_rule.random_rays(sample_data, 61 + lds_cache, 2000, floor_instance=3)
+        big = 2048 * 256 + 65
+        reps = -(-(big + 300) // len(rays))
+        rng = np.random.default_rng(5)
+        order = np.concatenate([np.arange(len(rays))] + [rng.permutation(len(rays)) for _ in range(reps - 1)])          # later repetitions shuffled: waves mix instances
+        many = np.ascontiguousarray(rays[order])
+        n = len(many)
+        assert big > 2048 * 256 and n >= big + 258
+        d_rays = hip.upload(many)
+        guard = np.full((n, 8), 0xABABABAB, dtype=np.uint32)
+        for flags in (0, ray_rule.ACCEPT_FIRST_HIT):
+            whole = rt64.trace_rays(rt64_lib, s.view, many, flags).view(np.uint32)          # host form: staged in chunks
+            first = rt64.trace_rays(rt64_lib, s.view, rays, flags).view(np.uint32)
+            assert (first.view(np.int32)[:, 3] >= 0).sum() > len(rays) // 20 and first[:, 5].any()
+            assert np.array_equal(whole, first[order]), flags
+            for count in (1, 63, 64, 65, 255, 256, 257, big):
+                d_guard = hip.upload(guard[:count + 258])
+                assert rt64_lib.TraceViewRaysDevice(s.view, d_rays, d_guard, count, flags, None) == 1, rt64_lib.last_error()
+                out = hip.download(d_guard, guard[:count + 258])
+                assert np.array_equal(out[:count], whole[:count]) and (out[count:] == 0xABABABAB).all(), (flags, count)
+                if count <= 257:
+                    h_guard = guard[:count + 258].copy()
+                    assert rt64_lib.TraceViewRays(s.view, many.ctypes.data, h_guard.ctypes.data, count, flags) == 1
+                    assert np.array_equal(h_guard[:count], whole[:count]) and (h_guard[count:] == 0xABABABAB).all(), (flags, count)
+    finally:
+        hip.close()
+        s.close()
+
+
+@pytest.mark.gpu
 def test_camera_ray_picking_agrees_with_the_instance_image(rt64_lib, sample_data):
     from sm64rt_legacy_renderer_amd import rt64
     w, h = 128, 72
