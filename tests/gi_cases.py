@@ -129,12 +129,13 @@ def make_case(sample_data, name):
 def rule_scene(case, frame, background):
     from sm64rt_legacy_renderer_amd import rt64
     data = case["data_at"](frame)
-    scene = MC.rule_scene(data, case["view"], frame)
-    rt = [i for i in data.instances if data.meshes[i.mesh].flags & rt64.MESH_RAYTRACE_ENABLED]
+    described = bool(case.get("sky_described"))                       # the cases of tests/sky_cases.py: `sky` is a description for tests/sky_rule.py
+    scene = MC.rule_scene(data, case["view"], frame, sky_described=described)
+    rt =[i for i in data.instances if data.meshes[i.mesh].flags & rt64.MESH_RAYTRACE_ENABLED]
     assert all(i.material.shadowAlphaMultiplier == (1.0 if i.material.solidAlphaMultiplier == 1.0 else 0.0) for i in rt)      # a shadow ray is stopped by an instance, or passes it freely
     scene["shadow"] = light_rule.BruteForceShadows([I["triangles"] for I, i in zip(scene["instances"], rt) if i.material.shadowAlphaMultiplier == 1.0])
     assert (background is not None) == case["background"]
-    assert not (case["background"] and data.sky is not None), "a sky term or a background image, not both"
+    assert described or not (case["background"] and data.sky is not None), "a constant sky term or a background image, not both"
     e = data.desc
     cam = LC.rule_inputs(data)["camera"]
     scene.update(giSamples=int(case["view"]["gi_samples"]), giBounces=int(case["bounces"]), giDiffuseStrength=float(e.giDiffuseStrength), giSkyStrength=float(e.giSkyStrength),

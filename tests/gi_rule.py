@@ -11,8 +11,8 @@ and the scene as the host sent it.  It predicts INDIRECT_LIGHT_RAW (rgb and alph
 
 Reference lines cited as (I:n) are IndirectRayGen.hlsl, (R:n) Random.hlsli, (S:n) BgSky.hlsli, (B:n) BlueNoise.hlsli.
 
-Out of scope: temporal reprojection, the SVGF guide and input folds of the resolve kernel, the sky plane's UV arithmetic (`scene["sky"]` is one constant texel
-value) and the HSL modifier, normal and specular maps at the bounce hit, hit lists past 16 entries, primary_spp > 1.
+Out of scope: temporal reprojection, the SVGF guide and input folds of the resolve kernel, normal and specular maps at the bounce hit, hit lists past 16
+entries, primary_spp > 1.
 """
 import math
 
@@ -20,12 +20,13 @@ import numpy as np
 
 import light_rule as L
 import mirror_rule as M
+import sky_rule as S
 from light_rule import F
+from sky_rule import fake_envmap_uv                             # (S:14-18) one definition: the background image takes it with a yaw offset of 0
 
 EPSILON = L.EPSILON
 DECISION_K = L.DECISION_K
 SINCOS_ERR = 6.2e-8                                  # direction spec D1: |sin, cos of 2 pi u as both sides evaluate them - the real ones|
-ANGLE_K = 8                                          # upper estimate of the float32 roundings of atan2 and the sum and fmod around it (S:15-16), in units of U x the angle
 LUMA = [float(np.float32(x)) for x in (0.2126, 0.7152, 0.0722)]
 SNORM16 = 32767.0
 
@@ -94,26 +95,12 @@ def bounce_direction(n, bn_x, bn_y, mutate=None):
 
 # ---- I8: the sky term -------------------------------------------------------------------------------------------------------------------------------
 
-def fake_envmap_uv(d):
-    """(S:14-18) with yawOffset 0: (fmod(atan2(x, -z) + pi, 2 pi), fmod(atan2(-y, sqrt(x^2 + z^2)) + pi, 2 pi)) / 2 pi.  Returns (u, v, du, dv): the error of a float32
-    evaluation is that of the angles -- the direction's own error seen from the axis, ANGLE_K roundings of the angle -- over 2 pi.  The fmod's wrap is no decision:
-    under WRAP addressing uv 0 and 1 are the same place."""
-    x, y, z = d
-    hx = np.hypot(x.v, z.v); hl = np.sqrt(hx * hx + y.v * y.v)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        yaw_e = np.where(hx > 0.0, (x.e + z.e) / hx, np.inf)
-        pitch_e = np.where(hl > 0.0, (x.e + y.e + z.e) / hl, np.inf)
-    yaw = np.fmod(np.arctan2(x.v, -z.v) + math.pi, 2.0 * math.pi)
-    pitch = np.fmod(np.arctan2(-y.v, hx) + math.pi, 2.0 * math.pi)
-    k = ANGLE_K * L.U * 2.0 * math.pi
-    return yaw / (2.0 * math.pi), pitch / (2.0 * math.pi), (yaw_e + k) / (2.0 * math.pi) + 2.0 * L.U, (pitch_e + k) / (2.0 * math.pi) + 2.0 * L.U
-
-
-def background_envmap(image, d):
-    """(S:91-93) LINEAR / WRAP level-0 sample of the stored IMAGE_BACKGROUND ((H, W, 4) bytes) at fake_envmap_uv(d): the uv error enters through the texels' local
-    differences (tests/sampler_rule.py evaluates the corners of the box).  Returns three F."""
+def background_envmap(image, d, yaw_offset=0.0):
+    """(S:91-93) LINEAR / WRAP level-0 sample of the stored IMAGE_BACKGROUND ((H, W, 4) bytes) at fake_envmap_uv(d) -- sky_rule's, with a yaw offset of 0 whatever the
+    sky's (only a wrong variant passes another): the uv error enters through the texels' local differences (tests/sampler_rule.py evaluates the corners of the box).
+    Returns three F."""
     import sampler_rule as SR
-    u, v, du, dv = fake_envmap_uv(d)
+    u, v, du, dv = fake_envmap_uv(d, yaw_offset)
     ok = np.isfinite(du) & np.isfinite(dv)
     zero = np.zeros((len(u), 2))
     r = SR.sample_grad_bounds([np.asarray(image)], u, v, zero, zero, SR.LINEAR, SR.WRAP, SR.WRAP, np.where(ok, du, 0.0), np.where(ok, dv, 0.0), 0.0, 8.0 * L.U)
@@ -121,9 +108,14 @@ def background_envmap(image, d):
 
 
 def sky_term(scene, d):
-    """(I:82-84) lerp(background_envmap(d), sky.rgb, sky.a): 0 without a background instance; the sky plane is one constant texel value (`scene["sky"]`, alpha 1) or absent."""
+    """(I:82-84) lerp(background_envmap(d), sky.rgb, sky.a): 0 without a background instance.  `scene["sky"]` is a sky description (tests/sky_rule.py: the plane is
+    sampled in the ray's direction, E1-E6), or one constant texel value with alpha `skyAlpha` (1 with a sky plane, 0 without)."""
     n = len(d[0].v)
-    bg = background_envmap(scene["background"], d) if scene.get("background") is not None else [F(np.zeros(n)) for _ in range(3)]
+    sky = scene["sky"]
+    offset = S.background_yaw_offset(sky) if S.described(sky) else 0.0
+    bg = background_envmap(scene["background"], d, offset) if scene.get("background") is not None else [F(np.zeros(n)) for _ in range(3)]
+    if S.described(sky):
+        return S.over_background(bg, S.plane_colour(sky, d), sky.get("mutate"))
     a = float(scene.get("skyAlpha", 0.0))
     return [L.lerp(bg[c], scene["sky"][c], a) for c in range(3)]
 
@@ -318,8 +310,12 @@ def ray_radiance(scene, origin, direction, px, py, slice_, more, second, counts,
         if mutate == "diffuse_strength_on_sky":
             weight = L.mul(weight, gd)
         term = L.mul(sky[c], weight)                                                                            # (I:123) either order of the two products: one more rounding
+        if S.described(scene["sky"]):                                                                           # nothing remains: the sky is not seen, whatever bound its colour has
+            term = L.where((weight.v == 0.0) & (weight.e == 0.0), 0.0, term)
         out.append(L.add(res, F(term.v, term.e + L.U * np.abs(term.v))))
     sky_seen = (np.stack([np.abs(s.v) for s in sky], axis=-1).max(axis=-1) > 0.0) & (R["a"].v > 0.0)
+    if scene.get("skySeen") is not None:
+        scene["skySeen"][py[sky_seen], px[sky_seen]] = True
     for k, x in (("hit", R["count"] > 0), ("miss", R["count"] == 0), ("lit", drawn & ~shadowed), ("shadowed", shadowed), ("two_contributing", R["contributing"] >= 2),
                  ("sky", sky_seen)):
         counts[k] = counts.get(k, 0) + int(x.sum())
@@ -335,8 +331,8 @@ def _f16_bound(v, e):
 def indirect(scene, position, normal, instance_id, mutate=None):
     """IndirectRayGen for every pixel of a frame without history.  position, normal: (H, W, >= 3) as stored; instance_id: (H, W) int.
 
-    scene: instances, lights, ambientBase, ambientNoGI, sky, bluenoise, frameCount, diSamples, shadow as tests/mirror_rule.py reads them, and skyAlpha (1 with a sky plane,
-    else 0), background (the stored IMAGE_BACKGROUND or None), giSamples, giBounces, giDiffuseStrength, giSkyStrength, eye (only a wrong variant reads it).
+    scene: instances, lights, ambientBase, ambientNoGI, sky (a description for tests/sky_rule.py, or the one constant term), bluenoise, frameCount, diSamples, shadow as tests/mirror_rule.py reads them, and skyAlpha (1 with a sky plane,
+    else 0), skySeen (optional (H, W) bool array: the rule marks the pixels one of whose rays sees the sky), background (the stored IMAGE_BACKGROUND or None), giSamples, giBounces, giDiffuseStrength, giSkyStrength, eye (only a wrong variant reads it).
     Returns dict: value, bound (H, W, 4) of INDIRECT_LIGHT_RAW (alpha = giSamples on a surface, 0 elsewhere: bound 0), moments, moments_bound (H, W, 2) of GI_MOMENTS,
     decided (H, W), surface (H, W), info (counts over the rays of the frame, undecided pixels)."""
     assert mutate is None or mutate in MUTATIONS, mutate

@@ -194,7 +194,8 @@ _MATERIAL = ("ignoreNormalFactor", "specularExponent", "shadowRayBias", "solidAl
              "refractionFactor", "fogMul", "fogOffset", "depthBias")
 
 
-def rule_scene(data, view, frame_count):
+def rule_scene(data, view, frame_count, sky_described=False):
+    """sky_described: `sky` is a description for tests/sky_rule.py (the cases of tests/sky_cases.py), not the one constant term."""
     from sm64rt_legacy_renderer_amd import rt64
     r = LC.rule_inputs(data)
     v3 = lambda x: (float(x.x), float(x.y), float(x.z))
@@ -222,7 +223,12 @@ def rule_scene(data, view, frame_count):
     sy = 1.0 / np.tan(0.5 * fov); sx = sy / (W / H); rng = zf / (zn - zf)
     proj = np.zeros((4, 4)); proj[0, 0] = sx; proj[1, 1] = sy; proj[2, 2] = rng; proj[2, 3] = -1.0; proj[3, 2] = rng * zn
     sky = [light_rule.F(0.0)] * 3
-    if data.sky is not None:
+    if data.sky is not None and sky_described:
+        e = data.desc
+        assert data.textures[data.sky].format == rt64.TEXTURE_FORMAT_RGBA8
+        sky = dict(texels=np.asarray(data.textures[data.sky].data), multiplier=v3(e.skyDiffuseMultiplier), hsl=v3(e.skyHSLModifier), yawOffset=float(e.skyYawOffset),
+                   camera=dict(view=np.asarray(data.view, dtype=np.float32), width=W, height=H, jitter=(0.0, 0.0)), tiled=False, mutate=None)
+    elif data.sky is not None:
         t = data.textures[data.sky].data
         assert (t == t[0, 0]).all() and t[0, 0, 3] == 255                     # one texel value, opaque: sky_finish(texel) whatever the UV
         e = data.desc

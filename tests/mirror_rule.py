@@ -11,12 +11,15 @@ k + 1 starts again from what pass k stored.
 
 Reference lines cited as (M:n) are ReflectionRayGen.hlsl, (G:n) RefractionRayGen.hlsl, (Fog:n) Fog.hlsli, (I:n) Instances.hlsli.
 
-Out of scope: the sky's UV arithmetic (the scenes have no sky, or one whose texels are all equal: `scene["sky"]` is that one term), the HSL modifier,
-normal and specular maps, texture gradients other than zero (a secondary ray carries none: level 0), the hit list past 16 entries, background instances.
+The sky a ray leaves into is tests/sky_rule.py's (E1-E8) where `scene["sky"]` is a sky description -- along the mirror ray, at the pixel's screen UV behind glass --
+else the one constant term of a scene whose sky texels are all equal.
+
+Out of scope: normal and specular maps, texture gradients other than zero (a secondary ray carries none: level 0), the hit list past 16 entries, background instances.
 """
 import numpy as np
 
 import light_rule as L
+import sky_rule as S
 from light_rule import F
 
 EPSILON = L.EPSILON
@@ -411,6 +414,8 @@ def reflection_pass(scene, position, view, normal, instance_id, reflection, muta
     R = _resolve(scene, origin, d, alpha, ids, False, mutate)
     light, lwhy, have = _lights(scene, R, d, px, py, mutate == "mirror_shadows", mutate)
     sky = scene["sky"]
+    if S.described(sky):                                                                                    # SampleSkyPlane along the mirror ray, over no background (E1-E6)
+        sky = S.over_background([F(np.zeros(n)) for _ in range(3)], S.plane_colour(sky, d), sky.get("mutate"))
     shine = np.asarray([I["material"]["reflectionShineFactor"] for I in scene["instances"]], dtype=np.float64)[ids]
     up = L.fmax(d[1], 0.0) if mutate != "shine_abs" else F(np.abs(d[1].v), d[1].e)
     down = L.fmax(L.neg(d[1]), 0.0) if mutate != "shine_abs" else F(np.abs(d[1].v), d[1].e)
@@ -446,7 +451,7 @@ def reflection_pass(scene, position, view, normal, instance_id, reflection, muta
     return dict(value=value, bound=bound, decided=decided, takes=takes, has_hit=full(has_hit), goes_on=full(goes),
                 state_position=(full(pos_v), full(pos_e + L.U * np.abs(pos_v))), state_direction=(full(dir_v), full(dir_b)), state_normal=(full(nrm_v), full(nrm_b)),
                 state_id=full(R["id"], -1),
-                info=dict(hits=full(R["count"]), contributing=full(R["contributing"]), textured=full(R["textured"]), lit_surface=full(have),
+                info=dict(hits=full(R["count"]), contributing=full(R["contributing"]), textured=full(R["textured"]), lit_surface=full(have), sky=full(R["a"].v > 0.0),
                           undecided={k_: int(v_.sum()) for k_, v_ in why.items()}, fresnel_alpha=full(na.v)))
 
 
@@ -485,6 +490,8 @@ def refraction_pass(scene, position, view, normal, instance_id, refraction, muta
     R = _resolve(scene, origin, d, alpha, ids, True, mutate)
     light, lwhy, have = _lights(scene, R, d, px, py, mutate != "glass_no_shadows", mutate)
     sky = scene["sky"]
+    if S.described(sky):                                                                                    # SampleSky2D at the PIXEL's screen UV, not along the bent ray (G:112; E2-E6)
+        sky = S.over_background([F(np.zeros(n)) for _ in range(3)], S.screen_colour(sky, sky["camera"], px, py, S.F16_STEP), sky.get("mutate"))
     vals, errs = [], []
     for c in range(3):
         rgb = L.where(have, L.mul(R["rgb"][c], L.add(R["ambient"][c], light[c])), R["rgb"][c])              # (G:108)
@@ -506,7 +513,7 @@ def refraction_pass(scene, position, view, normal, instance_id, refraction, muta
     def full(x, fill=0):
         a = np.full((h, w) + x.shape[1:], fill, dtype=x.dtype); a[takes] = x; return a
     return dict(value=value, bound=bound, decided=decided, takes=takes, total_internal=full(total),
-                info=dict(hits=full(R["count"]), contributing=full(R["contributing"]), textured=full(R["textured"]), lit_surface=full(have), undecided={k_: int(v_.sum()) for k_, v_ in why.items()}))
+                info=dict(hits=full(R["count"]), contributing=full(R["contributing"]), textured=full(R["textured"]), lit_surface=full(have), sky=full(R["a"].v > 0.0), undecided={k_: int(v_.sum()) for k_, v_ in why.items()}))
 
 
 def compare(stored, value, bound, decided, takes):

@@ -188,13 +188,19 @@ def make_case(sample_data, name):
 
 def _camera(case, frame):
     d = case["data_at"](frame)
-    return dict(view=np.asarray(d.view, dtype=np.float32), fov=float(np.float32(d.fov)), near=float(np.float32(d.near)), far=float(np.float32(d.far)), width=W, height=H)
+    w, h = _size(case)
+    return dict(view=np.asarray(d.view, dtype=np.float32), fov=float(np.float32(d.fov)), near=float(np.float32(d.near)), far=float(np.float32(d.far)), width=w, height=h)
+
+
+def _size(case):
+    """88 x 72, but for the cases of tests/sky_cases.py that set a size of their own (the aspect ratio enters the sky plane's UV)."""
+    return case.get("size", (W, H))
 
 
 def rule_inputs(case, frame, background=None):
     from sm64rt_legacy_renderer_amd import rt64
     data = case["data_at"](frame)
-    scene = MC.rule_scene(data, case["view"], frame)
+    scene = MC.rule_scene(data, case["view"], frame, sky_described=bool(case.get("sky_described")))
     rt = [i for i in data.instances if data.meshes[i.mesh].flags & rt64.MESH_RAYTRACE_ENABLED]
     for I, inst in zip(scene["instances"], rt):
         mesh = data.meshes[inst.mesh]
@@ -239,7 +245,7 @@ def oracle_session(case):
             for j, inst in changed:
                 o.set_instance(j, inst)
             o.data = d
-            ref = o.render(W, H, images=f in case["compared"], can_reproject=case["reproject_at"](f), diSamples=case["view"]["di_samples"],
+            ref = o.render(*_size(case), images=f in case["compared"], can_reproject=case["reproject_at"](f), diSamples=case["view"]["di_samples"],
                            maxLights=case["view"]["max_lights"], maxReflections=0, **up)
             if f in case["compared"]:
                 out[f] = {key: ref[name] for key, name in ORACLE_IMAGES.items()}
@@ -253,7 +259,7 @@ def gpu_session(rt64_lib, case, options=None, view=None, stats=None):
     """The same session on the device, with device options (a kernel path) and view-description overrides.  stats: a dict that receives {frame: FRAME_STATS}."""
     from sm64rt_legacy_renderer_amd import rt64, sample_scene
     out = {}
-    s = sample_scene.Rt64Scene(rt64_lib, case["data_at"](0), W, H, hip_device=0)
+    s = sample_scene.Rt64Scene(rt64_lib, case["data_at"](0), *_size(case), hip_device=0)
     try:
         up = dict(upscaler=UPSCALER_FSR, upscaler_mode=UPSCALER_MODE_NATIVE) if case["upscaler"] else {}
         s.set_view_description(**dict(case["view"], **dict(up, **(view or {}))))

@@ -9,10 +9,12 @@ only to what no decision touches (VIEW_DIRECTION).  It imports nothing from orac
 The rule's inputs are the scene as the host sent it and the cameras of this frame and the previous one -- never a stored image, except IMAGE_BACKGROUND for the
 background term.  Its outputs are, per image, a value and a bound that includes the storage step (half an f16 step, half a UNORM8 step; float32 images one rounding).
 
-Out of scope: the sky's UV arithmetic and the HSL modifier (no sky, or one whose texels are all equal: `scene["sky"]` is that one term); normal and
+The sky behind a pixel is tests/sky_rule.py's (E1-E8) where `scene["sky"]` is a sky description, else the one constant term of a scene whose sky texels are all equal.
+
+Out of scope: normal and
 specular maps and combiners other than mix-colour or TEX0 (H1-H12 hold them); the lod chosen by the primary ray differentials (textures have one level); hit lists past
 16 entries (test_gpu_kbuffer.py); optNoise alpha; primary_spp > 1; the history guides normal[cur] and depth[cur], which have no readback; how a raster background
-instance is drawn into IMAGE_BACKGROUND (tests/test_gpu_raster.py): the rule samples the image as stored.  A scene has a sky term or a background image, not both.
+instance is drawn into IMAGE_BACKGROUND (tests/test_gpu_raster.py): the rule samples the image as stored.  A scene has a constant sky term or a background image, not both; a described sky lies over the background by its alpha (E6).
 """
 import math
 
@@ -20,6 +22,7 @@ import numpy as np
 
 import light_rule as L
 import mirror_rule as M
+import sky_rule as S
 from light_rule import F
 
 EPSILON = L.EPSILON
@@ -356,7 +359,13 @@ def primary(scene, camera, mutate=None):
     reactive = peak if mutate == "reactive_unclamped" else M.fmin(peak, REACTIVE_CAP)
     reactive = M.fmin(reactive, 1.0)                                                                      # UNORM8 saturates
     bg = scene["sky"]                                                                                     # bg = lerp(background, sky.rgb, sky.a): sky.a is 1 (one opaque texel value) or no sky
-    if camera.get("background") is not None:
+    if S.described(bg):                                                                                   # ... or a sky description: SampleSky2D at the pixel's screen UV (tests/sky_rule.py, E2-E6)
+        back = [F(np.zeros(n)) for _ in range(3)]
+        if camera.get("background") is not None:
+            back = background(camera["background"], px.astype(np.float64), py.astype(np.float64), jx, jy, size, mutate)
+        colour = S.screen_colour(bg, dict(view=cam["view"], width=w, height=h, jitter=(jx, jy)), px, py)
+        bg = S.over_background(back, colour, bg.get("mutate"))
+    elif camera.get("background") is not None:
         assert all(float(np.abs(c.v).max()) == 0.0 for c in bg), "a sky term or a background image, not both"
         bg = background(camera["background"], px.astype(np.float64), py.astype(np.float64), jx, jy, size, mutate)
     rgb = [L.add(res_rgb[c], L.mul(bg[c], res_a)) for c in range(3)]
@@ -385,6 +394,7 @@ def primary(scene, camera, mutate=None):
     why["bound"] = np.zeros(n, dtype=bool)
     for v, b in images.values():
         why["bound"] |= ~np.isfinite(b).all(axis=-1).reshape(n)
+    why["bound"] |= ~np.isfinite(de).all(axis=-1)                                                          # DIFFUSE under a sky colour that is claimed nowhere (E7)
     und = np.zeros(n, dtype=bool)
     for x in why.values():
         und |= x
