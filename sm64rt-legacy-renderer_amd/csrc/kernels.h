@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
-#include "../../include/rt64_alpha.h"        // (includes rt64_material.h, rt64_surface.h and rt64_query.h)
+#include "../../include/rt64_lighting.h"     // (includes rt64_alpha.h, rt64_material.h, rt64_surface.h and rt64_query.h)
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -166,3 +166,8 @@ hipError_t launch_row_hit_count(const int32_t *hitInstance, uint32_t *counts, in
 // (device pointers, 16-byte aligned; lods 4) against the tables of P (rules K1-K10).  P.traversalStack as for launch_ray_query; both read the texture table of P as well.
 hipError_t launch_alpha_query(const FrameParams &P, const void *rays, const void *lods, void *hits, uint64_t count, uint32_t flags, hipStream_t s);
 hipError_t launch_visibility_query(const FrameParams &P, const void *rays, void *visibility, uint64_t count, uint32_t flags, hipStream_t s);
+
+// ---- lighting.hip ---------------------------------------------------------------------------------------------------
+// RT64_LightViewRayHits: `count` RT64_RAYs, their RT64_RAY_HITs and (lods != nullptr) one float lod per record -> RT64_RAY_LIGHTINGs (device pointers, 16-byte aligned;
+// lods 4) from the instance, texture and light tables of P, with one shadow walk per admitted light (rules P1-P11).  P.traversalStack as for launch_ray_query.
+hipError_t launch_hit_light(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *lighting, uint64_t count, hipStream_t s);

@@ -225,7 +225,7 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility;
+    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility, queryLighting;
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -2170,25 +2170,28 @@ static void query_overflow_check(Device *dev, const char *fn) {
 
 // What one call does with its records: the walk (query.hip), the surface records of hits (surface.hip), or both back to back.
 // QUERY_ALPHA / QUERY_VISIBILITY: walks that run the any-hit programs themselves (alpha_query.hip); each stands alone in `work`.
-enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2, QUERY_SHADE = 4, QUERY_ALPHA = 8, QUERY_VISIBILITY = 16 };
+enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2, QUERY_SHADE = 4, QUERY_ALPHA = 8, QUERY_VISIBILITY = 16, QUERY_LIGHT = 32 };
 
 // hostArrays: rays / hits / surfaces in host memory, staged in chunks through pinned memory on the device's stream.  Otherwise device arrays, on `stream` (NULL: the device's stream).
 // work = QUERY_TRACE: rays -> hits (RT64_TraceViewRays).  QUERY_RESOLVE: rays + hits -> surfaces (RT64_ResolveViewRayHits).  Both: rays -> hits -> surfaces, host arrays only,
 // and `hits` may be NULL (RT64_TraceViewRaySurfaces).  QUERY_SHADE in place of QUERY_RESOLVE: `surfaces` holds RT64_RAY_MATERIALs and `lods` (or NULL) travels with the rays
 // (RT64_ShadeViewRayHits, RT64_TraceViewRayMaterials; material.hip).  QUERY_ALPHA: rays (+ lods) -> hits (RT64_TraceViewRaysAlpha).  QUERY_VISIBILITY: rays -> RT64_RAY_VISIBILITYs,
-// handed in as `hits` (RT64_TraceViewRayVisibility).  Both read the texture table like QUERY_SHADE (K9).
+// handed in as `hits` (RT64_TraceViewRayVisibility).  Both read the texture table like QUERY_SHADE (K9).  QUERY_LIGHT in place of QUERY_SHADE: `surfaces` holds
+// RT64_RAY_LIGHTINGs (RT64_LightViewRayHits; lighting.hip, rules P1-P11); its kernel walks shadow rays, so it takes the spill slab like a walk.  With QUERY_ALPHA in front:
+// RT64_TraceViewRayLighting.
 static void run_view_query(const char *fn, View *v, const void *rays, void *hits, void *surfaces, size_t count, unsigned flags, void *stream, bool hostArrays, int work, const void *lods = nullptr) {
     auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
     const bool alpha = (work & QUERY_ALPHA) != 0, visibility = (work & QUERY_VISIBILITY) != 0, walk = (work & (QUERY_TRACE | QUERY_ALPHA | QUERY_VISIBILITY)) != 0;
-    const bool trace = (work & QUERY_TRACE) != 0, shade = (work & QUERY_SHADE) != 0, resolve = (work & (QUERY_RESOLVE | QUERY_SHADE)) != 0;
+    const bool trace = (work & QUERY_TRACE) != 0, shade = (work & QUERY_SHADE) != 0, light = (work & QUERY_LIGHT) != 0, resolve = (work & (QUERY_RESOLVE | QUERY_SHADE | QUERY_LIGHT)) != 0;
     if (!v) fail("NULL view.");
     if (visibility) { if (!rays || !hits) fail("NULL ray or visibility array."); }
     else if (!resolve) { if (!rays || !hits) fail("NULL ray or hit array."); }
-    else if (!rays || !surfaces || (!hits && !trace)) fail(shade ? "NULL ray, hit or material array." : "NULL ray, hit or surface array.");
+    else if (!rays || !surfaces || (!hits && !walk)) fail(light ? "NULL ray, hit or lighting array." : shade ? "NULL ray, hit or material array." : "NULL ray, hit or surface array.");
+    if (light && (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING)) fail("unknown flags (a lighting query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // P10
     if (visibility && (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING)) fail("unknown flags (a visibility query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // K3
     if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RAY_FLAG_ACCEPT_FIRST_HIT)) fail("unknown flags.");
     if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(surfaces)) & 15u))
-        fail(visibility ? "the ray and visibility arrays must be 16-byte aligned." : shade ? "the ray, hit and material arrays must be 16-byte aligned." : resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
+        fail(visibility ? "the ray and visibility arrays must be 16-byte aligned." : light ? "the ray, hit and lighting arrays must be 16-byte aligned." : shade ? "the ray, hit and material arrays must be 16-byte aligned." : resolve ? "the ray, hit and surface arrays must be 16-byte aligned." : "the ray and hit arrays must be 16-byte aligned.");
     if (!hostArrays && (reinterpret_cast<uintptr_t>(lods) & 3u)) fail("the lod array must be 4-byte aligned.");
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
@@ -2196,7 +2199,7 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     if (!q.valid) fail("the view has no frame to query (draw one first).");
     if (q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
     for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
-    if ((shade || alpha || visibility) && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
+    if ((shade || alpha || visibility || light) && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
     dev->use();
     query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
     if (count == 0) return;
@@ -2205,7 +2208,7 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     FrameParams P = q.P;
     P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
     P.tileTiming = nullptr; P.traversalStack = nullptr;
-    if (walk && q.needSpill) {         // the walk can outgrow its LDS entries: the query's own slab, sized for its launch
+    if ((walk || light) && q.needSpill) {         // the walk (the shadow walks of a lighting record) can outgrow its LDS entries: the query's own slab, sized for its launch
         const size_t words = ray_query_spill_bytes() / sizeof(uint32_t);
         if (dev->querySlab.count < words) {
             dev->querySlab.reserve(words);
@@ -2228,13 +2231,13 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     if (hostArrays) {
         // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | surfaces] down as far as the call wants them.
         // A walk's records (`hits`: RT64_RAY_HITs, or RT64_RAY_VISIBILITYs from their own device buffer) are made on the device and only come down.
-        static_assert(sizeof(RT64_RAY_MATERIAL) == sizeof(RT64_RAY_SURFACE), "one record size for both kinds of resolve");
+        static_assert(sizeof(RT64_RAY_MATERIAL) == sizeof(RT64_RAY_SURFACE) && sizeof(RT64_RAY_LIGHTING) == sizeof(RT64_RAY_SURFACE), "one record size for every kind of resolve");
         const size_t rayB = sizeof(RT64_RAY), hitB = visibility ? sizeof(RT64_RAY_VISIBILITY) : sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE), lodB = lods ? sizeof(float) : 0;
         const size_t upB = rayB + (walk ? 0 : hitB) + lodB, downB = ((walk && hits) ? hitB : 0) + (resolve ? surfB : 0);
         const size_t chunk = std::min<size_t>(count, (size_t)1 << (resolve ? 18 : 20));
         DevArray<uint8_t> &walked = visibility ? dev->queryVisibility : dev->queryHits;
         dev->queryRays.reserve(chunk * rayB); walked.reserve(chunk * hitB);
-        DevArray<uint8_t> &records = shade ? dev->queryMaterials : dev->querySurfaces;
+        DevArray<uint8_t> &records = light ? dev->queryLighting : shade ? dev->queryMaterials : dev->querySurfaces;
         if (resolve) records.reserve(chunk * surfB);
         if (lods) dev->queryLods.reserve(chunk * lodB);
         uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
@@ -2252,7 +2255,8 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
                 HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, at4, n * lodB, hipMemcpyHostToDevice, s));
             }
             if (walk) launch_walk(dev->queryRays.ptr, lods ? dev->queryLods.ptr : nullptr, walked.ptr, n);
-            if (shade) HIP_CHECK(launch_hit_material(R, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
+            if (light) HIP_CHECK(launch_hit_light(P, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
+            else if (shade) HIP_CHECK(launch_hit_material(R, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
             else if (resolve) HIP_CHECK(launch_hit_surface(R, dev->queryRays.ptr, dev->queryHits.ptr, records.ptr, n, s));
             uint8_t *down = pin;
             if (walk && hits) { HIP_CHECK(hipMemcpyAsync(down, walked.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
@@ -2263,6 +2267,7 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
         }
     }
     else if (walk) launch_walk(rays, lods, hits, count);
+    else if (light) HIP_CHECK(launch_hit_light(P, rays, hits, lods, surfaces, count, s));
     else if (shade) HIP_CHECK(launch_hit_material(R, rays, hits, lods, surfaces, count, s));
     else HIP_CHECK(launch_hit_surface(R, rays, hits, surfaces, count, s));
     if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
@@ -2465,6 +2470,16 @@ RT64_EXPORT int RT64_TraceViewRayVisibility(RT64_VIEW *view, const RT64_RAY *ray
 }
 RT64_EXPORT int RT64_TraceViewRayVisibilityDevice(RT64_VIEW *view, const void *rays, void *visibility, size_t count, unsigned int flags, void *stream) {
     RT64_TRY run_view_query("RT64_TraceViewRayVisibilityDevice", reinterpret_cast<View *>(view), rays, visibility, nullptr, count, flags, stream, false, QUERY_VISIBILITY); return 1; RT64_CATCH(0)
+}
+// include/rt64_lighting.h (rules P1-P11)
+RT64_EXPORT int RT64_LightViewRayHits(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, RT64_RAY_LIGHTING *lighting, size_t count) {
+    RT64_TRY run_view_query("RT64_LightViewRayHits", reinterpret_cast<View *>(view), rays, const_cast<RT64_RAY_HIT *>(hits), lighting, count, 0, nullptr, true, QUERY_LIGHT, lods); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_LightViewRayHitsDevice(RT64_VIEW *view, const void *rays, const void *hits, const void *lods, void *lighting, size_t count, void *stream) {
+    RT64_TRY run_view_query("RT64_LightViewRayHitsDevice", reinterpret_cast<View *>(view), rays, const_cast<void *>(hits), lighting, count, 0, stream, false, QUERY_LIGHT, lods); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayLighting(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, RT64_RAY_LIGHTING *lighting, size_t count, unsigned int flags) {
+    RT64_TRY run_view_query("RT64_TraceViewRayLighting", reinterpret_cast<View *>(view), rays, hits, lighting, count, flags, nullptr, true, QUERY_ALPHA | QUERY_LIGHT, lods); return 1; RT64_CATCH(0)
 }
 
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {

@@ -251,6 +251,13 @@ ALPHA_API = [
     ("TraceViewRayVisibilityDevice", "RT64_TraceViewRayVisibilityDevice", C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint, _P]),
 ]
 VISIBILITY_VALID, VISIBILITY_BLOCKED = 0x1, 0x2
+# include/rt64_lighting.h: direct-light records for hits (rules P1-P11), a list and a loader (RT64_LoadLibraryLighting) of its own
+LIGHTING_API = [
+    ("LightViewRayHits", "RT64_LightViewRayHits", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t]),
+    ("LightViewRayHitsDevice", "RT64_LightViewRayHitsDevice", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewRayLighting", "RT64_TraceViewRayLighting", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+LIGHTING_VALID, LIGHTING_BAD_HIT, LIGHTING_BACK_FACE, LIGHTING_UNLIT, LIGHTING_TRUNCATED = 0x01, 0x02, 0x04, 0x08, 0x10
 
 
 class RAY(C.Structure):
@@ -276,7 +283,13 @@ class RAY_VISIBILITY(C.Structure):
     _fields_ = [("visibility", C.c_float), ("flags", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
 
 
-assert C.sizeof(RAY_VISIBILITY) == 16
+class RAY_LIGHTING(C.Structure):
+    _fields_ = [("direct", C.c_float * 3), ("flags", C.c_uint), ("unshadowed", C.c_float * 3), ("lightsAdmitted", C.c_uint),
+                ("emitted", C.c_float * 3), ("lightsBlocked", C.c_uint), ("instance", C.c_int), ("primitive", C.c_uint),
+                ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
+
+
+assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64
 assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
 
 HALO_ROWS = 62
@@ -302,7 +315,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -414,3 +427,18 @@ def trace_visibility(lib, view, rays, flags=0, stream=None):
     as uint32 bits (read them through `.view(int32)`): what a frame's shadow ray returns for the ray, noise aside (rule K5).  NumPy arrays take the
     host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
     return _query(lib, view, "TraceViewRayVisibility", "TraceViewRayVisibilityDevice", [("in", rays), ("out", 4)], flags, stream)
+
+
+def light_hits(lib, view, rays, hits, lods=None, stream=None):
+    """RT64_LightViewRayHits: (N, 8) float32 rays, the (N, 8) float32 hits a trace returned for them and, optionally, (N,) float32 lods (None: level 0
+    for every record) -> (N, 16) float32 RT64_RAY_LIGHTINGs: direct rgb, flags, unshadowed rgb, lightsAdmitted, emitted rgb, lightsBlocked, then
+    instance, primitive, nodesVisited, trianglesTested (the integers as uint32 / int32 bits: read them through `.view(int32)`): the direct light of
+    the view's last frame at each hit, every admitted light once at its centre (rules P1-P11).  NumPy arrays take the host path; torch CUDA tensors
+    the device path, enqueued on `stream` like trace_rays."""
+    return _query(lib, view, "LightViewRayHits", "LightViewRayHitsDevice", [("in", rays), ("in", hits), ("lods", lods), ("out", 16)], None, stream)
+
+
+def trace_lighting(lib, view, rays, lods=None, flags=0):
+    """RT64_TraceViewRayLighting on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): the walk of trace_rays_alpha and the
+    records of light_hits in one staging round trip -> (hits (N, 8), lighting (N, 16)).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
+    return _query(lib, view, "TraceViewRayLighting", None, [("in", rays), ("out", 8), ("lods", lods), ("out", 16)], flags)
