@@ -61,21 +61,7 @@ DEV void light_columns(ShadeEnv &env, float *intensities, uint8_t *indices, uint
 //   [scene cache: P.cacheWords x 16 B][light intensities: slots x RT_BLOCK floats][light indices: slots x RT_BLOCK bytes], slots = min(lights, 16) + 1
 DEV uint32_t light_slots(PRef P) { return (P.lightCount < RT64_MAX_LIGHTS ? P.lightCount : (uint32_t)RT64_MAX_LIGHTS) + 1u; }
 
-// LDS scene cache, filled once per workgroup (all threads call it; ends with a barrier).  Layout in 16-byte words:
-//   [0, 4m)            one 64-byte record per TLAS leaf slot: (M[c], M[4+c], M[8+c], M[12+c]) for c = 0..2 of worldToObject, then
-//                      (instance | flags << 8 | word offset of its BLAS nodes << 16, depth bias, tris pointer lo, hi)
-//   [4m, 4m + 4 nT)    TLAS nodes, nT = max(m - 1, 1)
-//   [cacheNodeOffset)  the BLAS nodes of every instance (offsets assigned by View::update)
-// The host enables it (FrameParams::cacheWords != 0) when all of that is at most RT_CACHE_MAX_WORDS: small scenes, like the sample.
-// The image is assembled once per table change in HBM (scene_cache_image_kernel: the pointer chase tlasIndex -> instance -> node array
-// happens there, three dependent round trips); a workgroup's fill is then one flat copy whose loads are all in flight together.
-DEV void fill_scene_cache(PRef P, u32x4_lds *cache) {
-    typedef const u32x4 __attribute__((address_space(1))) *G4;
-    G4 src = reinterpret_cast<G4>(reinterpret_cast<uintptr_t>(P.cacheImage));
-    const uint32_t words = P.cacheWords;
-    for (uint32_t t = threadIdx.x; t < words; t += RT_BLOCK) cache[t] = src[t];
-    __syncthreads();
-}
+// The scene cache is filled once per workgroup by fill_scene_cache (trace.h: its layout, and the one-round-trip copy the query kernels share).
 
 // ---- the prologue of a ray kernel -------------------------------------------------------------------------------------------
 // The __shared__ arrays stay declared in the kernels (their sizes depend on the kernel's template arguments, their order is the LDS layout); these two

@@ -51,13 +51,10 @@ DEV bool query_ray_valid(const float o[3], const float d[3], float tmin, float t
 
 // ---- walk kernels ----------------------------------------------------------------------------------------------------------------------------------------------
 // The __shared__ arrays stay declared in the kernel (ldsStack's size depends on CACHED).  CACHED: the frame's LDS scene cache image is copied in once per workgroup
-// and the walk reads nodes and instance records from LDS.
+// (fill_scene_cache of trace.h, the frame kernels' own) and the walk reads nodes and instance records from LDS.
 #define QUERY_STACK_WORDS(CACHED) ((CACHED) ? RT_STACK_LDS_CACHED / 2 : RT_STACK_LDS)
 template <bool CACHED> DEV void fill_cache(PRef P, u32x4_lds *dynLds) {      // every thread takes part before any of them leaves its ray loop
-    if (!CACHED) return;
-    GIn src = QUERY_IN(P.cacheImage);
-    for (uint32_t t = threadIdx.x; t < P.cacheWords; t += RT_BLOCK) dynLds[t] = src[t];
-    __syncthreads();
+    if (CACHED) fill_scene_cache(P, dynLds);
 }
 // this lane's column in its wave's [entry][lane] block (wave64: a push / pop is one conflict-free ds access), and its slab in HBM.  A CACHED kernel then calls
 // stk.use_cache(dynLds) itself: handed through here, the cache pointer changes the register allocation of ray_query_kernel<*, true>.

@@ -39,15 +39,21 @@ DEV Weights weights_at(const RasterTri &t, float area, int64_t px, int64_t py) {
 DEV float interp(const Weights &w, float a0, float a1, float a2) { return ((w.q0 * a0 + w.q1 * a1) + w.q2 * a2) / w.qs; }
 
 
-// One pixel (x, y) against the whole list, in draw order.  wx0..wy1: the pixel rectangle of the calling wave (wave-uniform), a
-// triangle whose bounding box misses it costs a few scalar instructions.  dstBits is the pixel's RGBA8 value: read from *dstPixel on
-// the first covering triangle unless the caller already holds it (loaded = true); dirty tells the caller to write it back.
-// One pixel (x, y) against one record.
-DEV void raster_blend_record(const GpuRasterInstance *__restrict__ instances, const RasterTri &t, const GpuTexture *__restrict__ textures,
+// What decides whether a wave looks at a record at all: its pixel box and the pieces that follow it, bytes [48, 80) of the record.  The draw lists are written
+// before the kernels that walk them start (frame_prologue_kernel or the raster set-up, same stream) and by nothing while they run, the condition under which the
+// instance and texture tables go through the constant address space (shade.h): with the wave-uniform record index these are two scalar 16-byte loads.
+struct RasterBox { int32_t px0, py0, px1, py1; uint32_t inst, clipped, extraFirst, extraCount; };
+static_assert(offsetof(RasterTri, px0) == 48 && offsetof(RasterTri, extraCount) == 76 && sizeof(RasterBox) == 32, "RasterBox");
+DEV RasterBox raster_box(const RasterTri *t) { return load_const(reinterpret_cast<const RasterBox *>(&t->px0)); }
+
+// One pixel (x, y) against one record, b = raster_box(&t).  wx0..wy1: the pixel rectangle of the calling wave (wave-uniform): a record whose box misses it
+// costs four scalar compares on b and no vector load (read through `t`, the compiler makes each of the four box fields a global_load_dword with its own wait,
+// one behind the other at the end of every wave of the one-kernel frame).  A pixel the box covers reads the rest of the record through `t`.
+DEV void raster_blend_record(const GpuRasterInstance *__restrict__ instances, const RasterTri &t, const RasterBox &b, const GpuTexture *__restrict__ textures,
                              int x, int y, bool inside, int wx0, int wx1, int wy0, int wy1, const uint32_t *dstPixel, uint32_t &dstBits, bool &loaded, bool &dirty) {
     {
-        if (t.px0 > wx1 || t.px1 < wx0 || t.py0 > wy1 || t.py1 < wy0) return;            // uniform: scalar compares
-        if (!inside || x < t.px0 || x > t.px1 || y < t.py0 || y > t.py1) return;
+        if ((b.px0 > wx1) | (b.px1 < wx0) | (b.py0 > wy1) | (b.py1 < wy0)) return;        // uniform: scalar compares
+        if (!inside || x < b.px0 || x > b.px1 || y < b.py0 || y > b.py1) return;
         const int64_t cx = (int64_t)x * 256 + 128, cy = (int64_t)y * 256 + 128;
         const int64_t e12 = edge_fn(t, 1, 2, cx, cy), e20 = edge_fn(t, 2, 0, cx, cy), e01 = edge_fn(t, 0, 1, cx, cy);
         if (!edge_in(t, 1, 2, e12) || !edge_in(t, 2, 0, e20) || !edge_in(t, 0, 1, e01)) return;
@@ -101,16 +107,17 @@ DEV void raster_blend_record(const GpuRasterInstance *__restrict__ instances, co
 }
 
 // One pixel (x, y) against the whole list, in draw order.  wx0..wy1: the pixel rectangle of the calling wave (wave-uniform), a
-// triangle whose bounding box misses it costs a few scalar instructions.  dstBits is the pixel's RGBA8 value: read from *dstPixel on
+// triangle whose bounding box misses it costs two scalar loads and four scalar compares.  dstBits is the pixel's RGBA8 value: read from *dstPixel on
 // the first covering triangle unless the caller already holds it (loaded = true); dirty tells the caller to write it back.
 // The further pieces of a clipped triangle (S0) follow their first piece (they are disjoint, so their own order is immaterial).
 DEV void raster_blend_pixel(const GpuRasterInstance *__restrict__ instances, const RasterTri *__restrict__ tris, uint32_t triTotal, const GpuTexture *__restrict__ textures,
                             int x, int y, bool inside, int wx0, int wx1, int wy0, int wy1, const uint32_t *dstPixel, uint32_t &dstBits, bool &loaded, bool &dirty) {
     for (uint32_t n = 0; n < triTotal; n++) {
-        const RasterTri &t = tris[n];
-        raster_blend_record(instances, t, textures, x, y, inside, wx0, wx1, wy0, wy1, dstPixel, dstBits, loaded, dirty);
-        const uint32_t extra = t.extraCount;                                             // uniform
-        for (uint32_t e = 0; e < extra; e++)
-            raster_blend_record(instances, tris[t.extraFirst + e], textures, x, y, inside, wx0, wx1, wy0, wy1, dstPixel, dstBits, loaded, dirty);
+        const RasterBox b = raster_box(tris + n);                                        // uniform: scalar loads
+        raster_blend_record(instances, tris[n], b, textures, x, y, inside, wx0, wx1, wy0, wy1, dstPixel, dstBits, loaded, dirty);
+        for (uint32_t e = 0; e < b.extraCount; e++) {
+            const RasterTri *piece = tris + (b.extraFirst + e);
+            raster_blend_record(instances, *piece, raster_box(piece), textures, x, y, inside, wx0, wx1, wy0, wy1, dstPixel, dstBits, loaded, dirty);
+        }
     }
 }

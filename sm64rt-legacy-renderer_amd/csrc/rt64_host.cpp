@@ -1336,7 +1336,7 @@ void View::update() {                          // View::update, rt64_view.cpp:10
                 float mn[RT64_HOST_TLAS_MAX][3], mx[RT64_HOST_TLAS_MAX][3];
                 for (uint32_t i = 0; i < n; i++) { memcpy(mn[i], rtInstances[i].instance->mesh->hostBmin, 12); memcpy(mx[i], rtInstances[i].instance->mesh->hostBmax, 12); }
                 host_build_tlas(hInst, mn, mx, n, hn, hi, hm, hh);
-                if (hostCache) {        // head of the LDS scene cache image (layout: fill_scene_cache, passes.hip): one 64-byte record per TLAS leaf slot, then the TLAS nodes with 16-bit child references
+                if (hostCache) {        // head of the LDS scene cache image (layout: fill_scene_cache, trace.h): one 64-byte record per TLAS leaf slot, then the TLAS nodes with 16-bit child references
                     memset(pinnedStage + tlasAt + nodeBytes + sizeof(BlasHeader) + 2 * sizeof(uint32_t) * n, 0, cacheAt - (tlasAt + nodeBytes + sizeof(BlasHeader) + 2 * sizeof(uint32_t) * n));
                     uint32_t *cw = reinterpret_cast<uint32_t *>(pinnedStage + cacheAt);
                     for (uint32_t k = 0; k < n; k++) {

@@ -158,12 +158,44 @@ DEV GpuTri load_tri(const GpuTri *p) {                            // 3 x global_
 // CACHED: the scene's nodes and per-instance records sit in LDS (stk.cache, layout in fill_scene_cache): a node visit and an
 // instance entry are ds_read_b128s (~100 cycles) instead of dependent global loads (~1 us each under load); only triangles still come
 // from HBM/L2 (with them in LDS too -- 36 KB per workgroup instead of 21 -- the longer fill of every workgroup cost more than the L2
-// round trips it saved: C2 0.158 against 0.153 ms, profiles/r02_experiments/lds_triangles_*).  Same data, same arithmetic, same order:
-// results and visit counts are unchanged.
+// round trips it saved: C2 0.158 against 0.153 ms, profiles/r02_experiments/lds_triangles_*; that fill was a rolled loop with one load
+// in flight, three more serial trips to L2 per workgroup, so the figures price the loop and not the idea).  Same data, same arithmetic,
+// same order: results and visit counts are unchanged.
 DEV GpuNode load_node_lds(const u32x4_lds *q) {
     union { u32x4_lds w[4]; GpuNode n; } u;
     u.w[0] = q[0]; u.w[1] = q[1]; u.w[2] = q[2]; u.w[3] = q[3];
     return u.n;
+}
+
+// LDS scene cache, filled once per workgroup of RT_BLOCK threads (all of them call it; ends with a barrier).  Layout in 16-byte words:
+//   [0, 4m)            one 64-byte record per TLAS leaf slot: (M[c], M[4+c], M[8+c], M[12+c]) for c = 0..2 of worldToObject, then
+//                      (instance | flags << 8 | word offset of its BLAS nodes << 16, depth bias, tris pointer lo, hi)
+//   [4m, 4m + 4 nT)    TLAS nodes, nT = max(m - 1, 1)
+//   [cacheNodeOffset)  the BLAS nodes of every instance (offsets assigned by View::update)
+// The host enables it (FrameParams::cacheWords != 0) when all of that is at most RT_CACHE_MAX_WORDS: small scenes, like the sample.
+// The image is assembled once per table change in HBM (scene_cache_image_kernel: the pointer chase tlasIndex -> instance -> node array
+// happens there, three dependent round trips); a workgroup's fill is then one flat copy in one round trip: a thread issues all
+// RT_CACHE_MAX_WORDS / RT_BLOCK loads of its words before it waits for the first of them.  Written as a loop, or unrolled with each load
+// under its own `t < words`, the compiler waits for every load before it issues the next (one trip to L2 per 256 words, five to six for
+// the sample scene).  So the loads are unconditional -- a thread without a word in a chunk reads the image's last word again, never past
+// it -- and only the LDS stores are guarded; the empty asm between the two uses every loaded value, which keeps the compiler from sinking
+// a load into its store's branch.
+DEV void fill_scene_cache(PRef P, u32x4_lds *cache) {
+    constexpr uint32_t CHUNKS = RT_CACHE_MAX_WORDS / RT_BLOCK;
+    static_assert(RT_CACHE_MAX_WORDS % RT_BLOCK == 0, "the scene cache is filled in chunks of RT_BLOCK words");
+    GlobalU4 src = reinterpret_cast<GlobalU4>(reinterpret_cast<uintptr_t>(P.cacheImage));
+    const uint32_t words = P.cacheWords;
+    if (words != 0 && words <= (uint32_t)RT_CACHE_MAX_WORDS) {      // (uniform; the launchers take a CACHED kernel only for such a frame)
+        const uint32_t last = words - 1u;
+        u32x4 w[CHUNKS];
+#pragma unroll
+        for (uint32_t k = 0; k < CHUNKS; k++) { const uint32_t t = threadIdx.x + k * RT_BLOCK; w[k] = src[t < last ? t : last]; }
+#pragma unroll
+        for (uint32_t k = 0; k < CHUNKS; k++) asm volatile("" : "+v"(w[k]));
+#pragma unroll
+        for (uint32_t k = 0; k < CHUNKS; k++) { const uint32_t t = threadIdx.x + k * RT_BLOCK; if (t < words) cache[t] = w[k]; }
+    }
+    __syncthreads();
 }
 
 
