@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
 #include "../../include/rt64_lighting.h"     // (includes rt64_alpha.h, rt64_material.h, rt64_surface.h and rt64_query.h)
+#include "../../include/rt64_footprint.h"
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -171,3 +172,11 @@ hipError_t launch_visibility_query(const FrameParams &P, const void *rays, void 
 // RT64_LightViewRayHits: `count` RT64_RAYs, their RT64_RAY_HITs and (lods != nullptr) one float lod per record -> RT64_RAY_LIGHTINGs (device pointers, 16-byte aligned;
 // lods 4) from the instance, texture and light tables of P, with one shadow walk per admitted light (rules P1-P11).  P.traversalStack as for launch_ray_query.
 hipError_t launch_hit_light(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *lighting, uint64_t count, hipStream_t s);
+
+// ---- footprint.hip --------------------------------------------------------------------------------------------------
+// RT64_GenerateViewCameraRays: `count` pixels (x, y pairs of uint32, 8-byte aligned; nullptr: record i is pixel n = firstPixel + i of the frame, (n % P.width, n / P.width), and firstPixel + count <= P.width * P.height) -> the
+// RT64_RAYs the frame of P traced for them and (diffs != nullptr) their RT64_RAY_DIFFERENTIALs (device pointers, 16-byte aligned; rules F1-F3).  Reads only P.
+hipError_t launch_camera_rays(const FrameParams &P, const void *pixels, uint64_t firstPixel, void *rays, void *diffs, uint64_t count, hipStream_t s);
+// RT64_FootprintViewRayHits: `count` RT64_RAYs, their RT64_RAY_DIFFERENTIALs (nullptr: all 0) and RT64_RAY_HITs -> RT64_RAY_FOOTPRINTs (device pointers, 16-byte aligned) from the
+// instance and texture tables of P and the vertex and index arrays they point to; no texel is read (rules F4-F8).  Reads neither P.traversalStack nor the LDS scene cache.
+hipError_t launch_hit_footprint(const FrameParams &P, const void *rays, const void *diffs, const void *hits, void *footprints, uint64_t count, hipStream_t s);

@@ -225,7 +225,7 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility, queryLighting;
+    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility, queryLighting, queryPixels, queryDiffs, queryFootprints;
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -2168,6 +2168,55 @@ static void query_overflow_check(Device *dev, const char *fn) {
                              std::to_string(RT_STACK_LDS + RT_STACK_SPILL) + " levels): their hits are missing geometry.");
 }
 
+// What every query checks of the frame it reads before it touches the device.  meshes: the call reads BLASes, vertex or index arrays (Q7 / A9: they must still be
+// the ones the frame traced); textures: it reads the texture table (H11).
+template <class Fail> static void query_frame_check(const View::QueryScene &q, bool meshes, bool textures, Fail &&fail) {
+    if (!q.valid) fail("the view has no frame to query (draw one first).");
+    if (meshes && q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
+    if (meshes) for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
+    if (textures && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
+}
+
+// The parameters and the stream of one query call (count > 0), ordered behind the view's last frame.  slab: the call walks (or lights): it gets the query's spill slab
+// when the scene needs one.  callerStream: the stream of a device-array form, or NULL for the device's own.
+static FrameParams query_start(Device *dev, View *v, bool slab, void *callerStream, hipStream_t &s) {
+    const View::QueryScene &q = v->query;
+    dev->enter();                                // the device's stream is now behind every render stream: behind the last frame
+    v->pruneQueryEvents(false);
+    FrameParams P = q.P;
+    P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
+    P.tileTiming = nullptr; P.traversalStack = nullptr;
+    if (slab && q.needSpill) {         // the walk (the shadow walks of a lighting record) can outgrow its LDS entries: the query's own slab, sized for its launch
+        const size_t words = ray_query_spill_bytes() / sizeof(uint32_t);
+        if (dev->querySlab.count < words) {
+            dev->querySlab.reserve(words);
+            void *flagDev = nullptr;
+            HIP_CHECK(hipHostGetDevicePointer(&flagDev, dev->queryOverflow, 0));
+            HIP_CHECK(launch_stack_slab_init(dev->querySlab.ptr, words / (RT_STACK_SPILL_HEADER + RT_STACK_SPILL), static_cast<const uint32_t *>(flagDev), dev->stream));
+        }
+        P.traversalStack = dev->querySlab.ptr;
+    }
+    s = callerStream ? static_cast<hipStream_t>(callerStream) : dev->stream;
+    if (s != dev->stream) { HIP_CHECK(hipEventRecord(dev->queryOrder, dev->stream)); HIP_CHECK(hipStreamWaitEvent(s, dev->queryOrder, 0)); }
+    if (P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slab
+    return P;
+}
+
+// Behind the last launch of a query call: the slab's turn ends; an enqueued call leaves its event with the table slot, any other waits and reports dropped stack entries.
+static void query_finish(const char *fn, Device *dev, View *v, const FrameParams &P, hipStream_t s) {
+    if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
+    if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes and the vertex / index arrays) stay as they are until the query has run
+        hipEvent_t done = nullptr;
+        HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        const hipError_t e = hipEventRecord(done, s);
+        if (e != hipSuccess) { hipEventDestroy(done); HIP_CHECK(e); }
+        v->tab[v->query.slot].queryEvents.push_back(done);
+        return;
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    query_overflow_check(dev, fn);
+}
+
 // What one call does with its records: the walk (query.hip), the surface records of hits (surface.hip), or both back to back.
 // QUERY_ALPHA / QUERY_VISIBILITY: walks that run the any-hit programs themselves (alpha_query.hip); each stands alone in `work`.
 enum : int { QUERY_TRACE = 1, QUERY_RESOLVE = 2, QUERY_SHADE = 4, QUERY_ALPHA = 8, QUERY_VISIBILITY = 16, QUERY_LIGHT = 32 };
@@ -2195,32 +2244,12 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     if (!hostArrays && (reinterpret_cast<uintptr_t>(lods) & 3u)) fail("the lod array must be 4-byte aligned.");
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
-    // Q7 / A9: the BLASes the frame traced, and the vertex and index arrays they were built from, must still be the ones it traced
-    if (!q.valid) fail("the view has no frame to query (draw one first).");
-    if (q.meshDestroyed) fail("a mesh the view's last frame traced was destroyed since; draw a frame first.");
-    for (const auto &m : q.meshes) if (m.first->version != m.second) fail("a mesh the view's last frame traced was changed by RT64_SetMesh since; draw a frame first.");
-    if ((shade || alpha || visibility || light) && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
+    query_frame_check(q, true, shade || alpha || visibility || light, fail);
     dev->use();
     query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
     if (count == 0) return;
-    dev->enter();                                // the device's stream is now behind every render stream: behind the last frame
-    v->pruneQueryEvents(false);
-    FrameParams P = q.P;
-    P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
-    P.tileTiming = nullptr; P.traversalStack = nullptr;
-    if ((walk || light) && q.needSpill) {         // the walk (the shadow walks of a lighting record) can outgrow its LDS entries: the query's own slab, sized for its launch
-        const size_t words = ray_query_spill_bytes() / sizeof(uint32_t);
-        if (dev->querySlab.count < words) {
-            dev->querySlab.reserve(words);
-            void *flagDev = nullptr;
-            HIP_CHECK(hipHostGetDevicePointer(&flagDev, dev->queryOverflow, 0));
-            HIP_CHECK(launch_stack_slab_init(dev->querySlab.ptr, words / (RT_STACK_SPILL_HEADER + RT_STACK_SPILL), static_cast<const uint32_t *>(flagDev), dev->stream));
-        }
-        P.traversalStack = dev->querySlab.ptr;
-    }
-    const hipStream_t s = (!hostArrays && stream) ? static_cast<hipStream_t>(stream) : dev->stream;
-    if (s != dev->stream) { HIP_CHECK(hipEventRecord(dev->queryOrder, dev->stream)); HIP_CHECK(hipStreamWaitEvent(s, dev->queryOrder, 0)); }
-    if (P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slab
+    hipStream_t s;
+    const FrameParams P = query_start(dev, v, walk || light, hostArrays ? nullptr : stream, s);
     FrameParams R = P; R.traversalStack = nullptr;                    // the resolve reads the instance table and what it points to: no stack, no slab
     // the walk of the call, if it has one, on device arrays: rays (+ lods) -> RT64_RAY_HITs, or 16-byte RT64_RAY_VISIBILITYs, in `out`
     auto launch_walk = [&](const void *r, const void *l, void *out, size_t n) {
@@ -2270,17 +2299,90 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     else if (light) HIP_CHECK(launch_hit_light(P, rays, hits, lods, surfaces, count, s));
     else if (shade) HIP_CHECK(launch_hit_material(R, rays, hits, lods, surfaces, count, s));
     else HIP_CHECK(launch_hit_surface(R, rays, hits, surfaces, count, s));
-    if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
-    if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes and the vertex / index arrays) stay as they are until the query has run
-        hipEvent_t done = nullptr;
-        HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        const hipError_t e = hipEventRecord(done, s);
-        if (e != hipSuccess) { hipEventDestroy(done); HIP_CHECK(e); }
-        v->tab[q.slot].queryEvents.push_back(done);
-        return;
+    query_finish(fn, dev, v, P, s);
+}
+
+// The calls of include/rt64_footprint.h (footprint.hip; rules F1-F11), beside run_view_query: their array sets differ -- pixels in, two outputs.
+// FOOTPRINT_GENERATE: pixels (or NULL) -> rays (+ diffs unless NULL).  FOOTPRINT_RECORDS: rays + diffs (or NULL) + hits -> footprints.  Both with FOOTPRINT_WALK between them,
+// host arrays only: pixels -> rays -> RT64_TraceViewRays' hits -> footprints, `rays` and `hits` optional outputs (RT64_TraceViewPixelFootprints).
+enum : int { FOOTPRINT_GENERATE = 1, FOOTPRINT_WALK = 2, FOOTPRINT_RECORDS = 4 };
+static void run_view_footprint(const char *fn, View *v, const void *pixels, void *rays, void *diffs, void *hits, void *footprints, size_t count, unsigned flags, void *stream, bool hostArrays, int work) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool generate = (work & FOOTPRINT_GENERATE) != 0, walk = (work & FOOTPRINT_WALK) != 0, records = (work & FOOTPRINT_RECORDS) != 0;
+    if (!v) fail("NULL view.");
+    if (walk) { if (!footprints) fail("NULL footprint array."); }
+    else if (generate) { if (!rays) fail("NULL ray array."); }
+    else if (!rays || !hits || !footprints) fail("NULL ray, hit or footprint array.");
+    if (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING) fail("unknown flags (a footprint query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // F10
+    if (!hostArrays) {
+        if (generate && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(diffs)) & 15u)) fail("the ray and differential arrays must be 16-byte aligned.");
+        if (generate && (reinterpret_cast<uintptr_t>(pixels) & 7u)) fail("the pixel array must be 8-byte aligned.");
+        if (records && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(diffs) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(footprints)) & 15u))
+            fail("the ray, differential, hit and footprint arrays must be 16-byte aligned.");
     }
-    HIP_CHECK(hipStreamSynchronize(s));
-    query_overflow_check(dev, fn);
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    query_frame_check(q, walk || records, records, fail);          // F10: the generate calls read no mesh and no texture
+    if (generate && (q.P.width <= 0 || q.P.height <= 0)) fail("the view's last frame traced no instance: it kept no camera to make rays from.");
+    if (generate && !pixels && count > (size_t)q.P.width * (size_t)q.P.height) fail("more rays than the frame has pixels (pixels = NULL counts them row by row).");      // F1
+    dev->use();
+    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
+    if (count == 0) return;
+    hipStream_t s;
+    const FrameParams P = query_start(dev, v, walk, hostArrays ? nullptr : stream, s);
+    FrameParams R = P; R.traversalStack = nullptr;                    // the generate and footprint kernels: no stack, no slab
+    if (hostArrays) {
+        // One round trip per chunk: [pixels] or [rays | diffs | hits] up, the kernels back to back, [rays | diffs], [footprints] or [rays | hits | footprints] down as far as the call wants them.
+        const size_t pixB = 2 * sizeof(uint32_t), rayB = sizeof(RT64_RAY), difB = sizeof(RT64_RAY_DIFFERENTIAL), hitB = sizeof(RT64_RAY_HIT), recB = sizeof(RT64_RAY_FOOTPRINT);
+        const bool diffsUp = !generate && diffs, diffsDown = generate && !walk && diffs, raysDown = generate && rays, hitsDown = walk && hits;
+        const size_t upB = generate ? (pixels ? pixB : 0) : rayB + (diffsUp ? difB : 0) + hitB;
+        const size_t downB = (raysDown ? rayB : 0) + (diffsDown ? difB : 0) + (hitsDown ? hitB : 0) + (records ? recB : 0);
+        const size_t chunk = std::min<size_t>(count, (size_t)1 << 18);
+        dev->queryRays.reserve(chunk * rayB);
+        if (generate && pixels) dev->queryPixels.reserve(chunk * pixB);
+        if (diffsUp || diffsDown || walk) dev->queryDiffs.reserve(chunk * difB);
+        if (walk || records) dev->queryHits.reserve(chunk * hitB);
+        if (records) dev->queryFootprints.reserve(chunk * recB);
+        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
+        const bool useDiffs = walk || diffsUp;          // the footprint kernel's differential: the one just generated, or the caller's
+        for (size_t at = 0; at < count; at += chunk) {
+            const size_t n = std::min(chunk, count - at);
+            if (generate) {
+                if (pixels) {
+                    memcpy(pin, static_cast<const uint8_t *>(pixels) + at * pixB, n * pixB);
+                    HIP_CHECK(hipMemcpyAsync(dev->queryPixels.ptr, pin, n * pixB, hipMemcpyHostToDevice, s));
+                }
+                // (pixels = NULL: record i of the chunk is pixel at + i of the frame)
+                HIP_CHECK(launch_camera_rays(R, pixels ? dev->queryPixels.ptr : nullptr, at, dev->queryRays.ptr, (walk || diffsDown) ? dev->queryDiffs.ptr : nullptr, n, s));
+            }
+            else {
+                uint8_t *up = pin;
+                memcpy(up, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, up, n * rayB, hipMemcpyHostToDevice, s)); up += n * rayB;
+                if (diffsUp) {
+                    memcpy(up, static_cast<const uint8_t *>(diffs) + at * difB, n * difB);
+                    HIP_CHECK(hipMemcpyAsync(dev->queryDiffs.ptr, up, n * difB, hipMemcpyHostToDevice, s)); up += n * difB;
+                }
+                memcpy(up, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, up, n * hitB, hipMemcpyHostToDevice, s));
+            }
+            if (walk) HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
+            if (records) HIP_CHECK(launch_hit_footprint(R, dev->queryRays.ptr, useDiffs ? dev->queryDiffs.ptr : nullptr, dev->queryHits.ptr, dev->queryFootprints.ptr, n, s));
+            uint8_t *down = pin, *raysAt = nullptr, *diffsAt = nullptr, *hitsAt = nullptr, *recAt = nullptr;
+            if (raysDown) { raysAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryRays.ptr, n * rayB, hipMemcpyDeviceToHost, s)); down += n * rayB; }
+            if (diffsDown) { diffsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryDiffs.ptr, n * difB, hipMemcpyDeviceToHost, s)); down += n * difB; }
+            if (hitsDown) { hitsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
+            if (records) { recAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryFootprints.ptr, n * recB, hipMemcpyDeviceToHost, s)); }
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (raysAt) memcpy(static_cast<uint8_t *>(rays) + at * rayB, raysAt, n * rayB);
+            if (diffsAt) memcpy(static_cast<uint8_t *>(diffs) + at * difB, diffsAt, n * difB);
+            if (hitsAt) memcpy(static_cast<uint8_t *>(hits) + at * hitB, hitsAt, n * hitB);
+            if (recAt) memcpy(static_cast<uint8_t *>(footprints) + at * recB, recAt, n * recB);
+        }
+    }
+    else if (generate) HIP_CHECK(launch_camera_rays(R, pixels, 0, rays, diffs, count, s));
+    else HIP_CHECK(launch_hit_footprint(R, rays, diffs, hits, footprints, count, s));
+    query_finish(fn, dev, v, P, s);
 }
 
 }  // namespace rt64
@@ -2480,6 +2582,23 @@ RT64_EXPORT int RT64_LightViewRayHitsDevice(RT64_VIEW *view, const void *rays, c
 }
 RT64_EXPORT int RT64_TraceViewRayLighting(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, RT64_RAY_LIGHTING *lighting, size_t count, unsigned int flags) {
     RT64_TRY run_view_query("RT64_TraceViewRayLighting", reinterpret_cast<View *>(view), rays, hits, lighting, count, flags, nullptr, true, QUERY_ALPHA | QUERY_LIGHT, lods); return 1; RT64_CATCH(0)
+}
+// include/rt64_footprint.h (rules F1-F11)
+RT64_EXPORT int RT64_GenerateViewCameraRays(RT64_VIEW *view, const unsigned int *pixels, RT64_RAY *rays, RT64_RAY_DIFFERENTIAL *diffs, size_t count) {
+    RT64_TRY run_view_footprint("RT64_GenerateViewCameraRays", reinterpret_cast<View *>(view), pixels, rays, diffs, nullptr, nullptr, count, 0, nullptr, true, FOOTPRINT_GENERATE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_GenerateViewCameraRaysDevice(RT64_VIEW *view, const void *pixels, void *rays, void *diffs, size_t count, void *stream) {
+    RT64_TRY run_view_footprint("RT64_GenerateViewCameraRaysDevice", reinterpret_cast<View *>(view), pixels, rays, diffs, nullptr, nullptr, count, 0, stream, false, FOOTPRINT_GENERATE); return 1; RT64_CATCH(0)
+}
+// (the const casts only fit the shared signature: these two write neither rays, diffs nor hits)
+RT64_EXPORT int RT64_FootprintViewRayHits(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_DIFFERENTIAL *diffs, const RT64_RAY_HIT *hits, RT64_RAY_FOOTPRINT *footprints, size_t count) {
+    RT64_TRY run_view_footprint("RT64_FootprintViewRayHits", reinterpret_cast<View *>(view), nullptr, const_cast<RT64_RAY *>(rays), const_cast<RT64_RAY_DIFFERENTIAL *>(diffs), const_cast<RT64_RAY_HIT *>(hits), footprints, count, 0, nullptr, true, FOOTPRINT_RECORDS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_FootprintViewRayHitsDevice(RT64_VIEW *view, const void *rays, const void *diffs, const void *hits, void *footprints, size_t count, void *stream) {
+    RT64_TRY run_view_footprint("RT64_FootprintViewRayHitsDevice", reinterpret_cast<View *>(view), nullptr, const_cast<void *>(rays), const_cast<void *>(diffs), const_cast<void *>(hits), footprints, count, 0, stream, false, FOOTPRINT_RECORDS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewPixelFootprints(RT64_VIEW *view, const unsigned int *pixels, RT64_RAY *rays, RT64_RAY_HIT *hits, RT64_RAY_FOOTPRINT *footprints, size_t count, unsigned int flags) {
+    RT64_TRY run_view_footprint("RT64_TraceViewPixelFootprints", reinterpret_cast<View *>(view), pixels, rays, nullptr, hits, footprints, count, flags, nullptr, true, FOOTPRINT_GENERATE | FOOTPRINT_WALK | FOOTPRINT_RECORDS); return 1; RT64_CATCH(0)
 }
 
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {

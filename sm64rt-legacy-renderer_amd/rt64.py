@@ -258,6 +258,15 @@ LIGHTING_API = [
     ("TraceViewRayLighting", "RT64_TraceViewRayLighting", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
 ]
 LIGHTING_VALID, LIGHTING_BAD_HIT, LIGHTING_BACK_FACE, LIGHTING_UNLIT, LIGHTING_TRUNCATED = 0x01, 0x02, 0x04, 0x08, 0x10
+# include/rt64_footprint.h: camera rays with differentials and texture footprints for hits (rules F1-F11), a list and a loader (RT64_LoadLibraryFootprint) of its own
+FOOTPRINT_API = [
+    ("GenerateViewCameraRays", "RT64_GenerateViewCameraRays", C.c_int, [_P, _P, _P, _P, C.c_size_t]),
+    ("GenerateViewCameraRaysDevice", "RT64_GenerateViewCameraRaysDevice", C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
+    ("FootprintViewRayHits", "RT64_FootprintViewRayHits", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t]),
+    ("FootprintViewRayHitsDevice", "RT64_FootprintViewRayHitsDevice", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewPixelFootprints", "RT64_TraceViewPixelFootprints", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+FOOTPRINT_VALID, FOOTPRINT_BAD_HIT, FOOTPRINT_HAS_UV, FOOTPRINT_TEXTURED = 0x01, 0x02, 0x04, 0x08
 
 
 class RAY(C.Structure):
@@ -289,7 +298,18 @@ class RAY_LIGHTING(C.Structure):
                 ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
 
 
+class RAY_DIFFERENTIAL(C.Structure):
+    _fields_ = [("dOdx", C.c_float * 3), ("reserved0", C.c_uint), ("dOdy", C.c_float * 3), ("reserved1", C.c_uint),
+                ("dDdx", C.c_float * 3), ("reserved2", C.c_uint), ("dDdy", C.c_float * 3), ("reserved3", C.c_uint)]
+
+
+class RAY_FOOTPRINT(C.Structure):
+    _fields_ = [("duvdx", C.c_float * 2), ("duvdy", C.c_float * 2), ("lod", C.c_float), ("lodNormal", C.c_float), ("lodSpecular", C.c_float),
+                ("flags", C.c_uint), ("dPdx", C.c_float * 3), ("instance", C.c_int), ("dPdy", C.c_float * 3), ("primitive", C.c_uint)]
+
+
 assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64
+assert C.sizeof(RAY_DIFFERENTIAL) == 64 and C.sizeof(RAY_FOOTPRINT) == 64
 assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
 
 HALO_ROWS = 62
@@ -315,7 +335,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -333,12 +353,14 @@ def exported_symbols():
 
 def _query(lib, view, host, device, args, flags=None, stream=None):
     """The call behind every ray-query wrapper.  `args` lists the entry point's array arguments in its order as (kind, value) pairs: ("in", an (N, 8)
-    float32 array: rays, hits), ("lods", an (N,) float32 array, or None for NULL), ("out", the width of an (N, width) float32 array to allocate).
+    float32 array: rays, hits), ("lods", an (N,) float32 array, or None for NULL), ("diffs", an (N, 16) float32 array of RT64_RAY_DIFFERENTIALs, or None for
+    NULL), ("out", the width of an (N, width) float32 array to allocate).
     NumPy inputs go to the entry point `host`; torch tensors to `device` (None: the call has no device form), enqueued on `stream`.  Behind the
     arrays go count, flags (unless None) and the stream.  Returns the outputs in order; raises ValueError for a wrong array,
     RuntimeError(RT64_GetLastError) on a refusal."""
     ins = [v for kind, v in args if kind == "in"]
     lods = next((v for kind, v in args if kind == "lods"), None)
+    diffs = next((v for kind, v in args if kind == "diffs"), None)
     on_device = device is not None and type(ins[0]).__module__.split(".")[0] == "torch"
     if on_device:
         import torch
@@ -349,7 +371,10 @@ def _query(lib, view, host, device, args, flags=None, stream=None):
             raise ValueError("one hit per ray")
         if lods is not None and (lods.dim() != 1 or lods.shape[0] != ins[0].shape[0] or lods.dtype != torch.float32 or not lods.is_cuda):
             raise ValueError("lods: an (N,) float32 CUDA tensor")
+        if diffs is not None and (diffs.dim() != 2 or tuple(diffs.shape) != (ins[0].shape[0], 16) or diffs.dtype != torch.float32 or not diffs.is_cuda):
+            raise ValueError("diffs: an (N, 16) float32 CUDA tensor")
         ins, lods = [a.contiguous() for a in ins], lods.contiguous() if lods is not None else None
+        diffs = diffs.contiguous() if diffs is not None else None
         new = lambda width: torch.empty((ins[0].shape[0], width), dtype=torch.float32, device=ins[0].device)
         address = lambda a: a.data_ptr()
     else:
@@ -361,10 +386,14 @@ def _query(lib, view, host, device, args, flags=None, stream=None):
             lods = np.ascontiguousarray(lods, dtype=np.float32)
             if lods.shape != (ins[0].shape[0],):
                 raise ValueError("lods: an (N,) float32 array")
+        if diffs is not None:
+            diffs = np.ascontiguousarray(diffs, dtype=np.float32)
+            if diffs.shape != (ins[0].shape[0], 16):
+                raise ValueError("diffs: an (N, 16) float32 array")
         new = lambda width: np.empty((ins[0].shape[0], width), dtype=np.float32)
         address = lambda a: a.ctypes.data
     checked = iter(ins)
-    arrays = [next(checked) if kind == "in" else lods if kind == "lods" else new(v) for kind, v in args]          # the entry point's arrays, in its order
+    arrays = [next(checked) if kind == "in" else lods if kind == "lods" else diffs if kind == "diffs" else new(v) for kind, v in args]          # the entry point's arrays, in its order
     outs = [a for (kind, _), a in zip(args, arrays) if kind == "out"]
     tail = []
     if on_device:
@@ -442,3 +471,73 @@ def trace_lighting(lib, view, rays, lods=None, flags=0):
     """RT64_TraceViewRayLighting on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): the walk of trace_rays_alpha and the
     records of light_hits in one staging round trip -> (hits (N, 8), lighting (N, 16)).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
     return _query(lib, view, "TraceViewRayLighting", None, [("in", rays), ("out", 8), ("lods", lods), ("out", 16)], flags)
+
+
+def _pixel_query(lib, view, host, device, pixels, count, widths, flags=None, stream=None):
+    """_query's sibling for the calls that start from pixels: `pixels` is an (N, 2) uint32 array of (x, y) pairs -- NumPy: the entry point `host`; a torch CUDA tensor
+    (int32 or uint32 bits): `device`, enqueued on `stream` -- or None with `count`: the first `count` pixels of the frame row by row, on the host path unless `stream`
+    (a torch stream) names the device one.  `widths` lists the outputs in the entry point's order: the width of an (N, width) float32 array to allocate, or None for
+    NULL.  Returns the allocated outputs in order."""
+    on_device = device is not None and (type(pixels).__module__.split(".")[0] == "torch" or (pixels is None and stream is not None))
+    if pixels is None:
+        if count is None or int(count) < 0:
+            raise ValueError("pixels=None needs a count")
+        n = int(count)
+    elif count is not None:
+        raise ValueError("count goes with pixels=None only")
+    if on_device:
+        import torch
+        if pixels is not None:
+            if pixels.dim() != 2 or pixels.shape[1] != 2 or pixels.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not pixels.is_cuda:
+                raise ValueError("pixels: an (N, 2) uint32 / int32 CUDA tensor")
+            pixels = pixels.contiguous()
+            n, where = pixels.shape[0], pixels.device
+        else:
+            where = torch.device("cuda", torch.cuda.current_device())
+        new = lambda width: torch.empty((n, width), dtype=torch.float32, device=where)
+        address = lambda a: a.data_ptr()
+    else:
+        import numpy as np
+        if pixels is not None:
+            pixels = np.ascontiguousarray(pixels, dtype=np.uint32)
+            if pixels.ndim != 2 or pixels.shape[1] != 2:
+                raise ValueError("pixels: an (N, 2) uint32 array")
+            n = pixels.shape[0]
+        new = lambda width: np.empty((n, width), dtype=np.float32)
+        address = lambda a: a.ctypes.data
+    outs = [new(w) if w is not None else None for w in widths]
+    tail = []
+    if on_device:
+        s = stream if stream is not None else torch.cuda.current_stream(where)
+        if s != torch.cuda.current_stream(where):
+            for a in [pixels] + outs:          # (the allocator must not hand the memory out again before the query has run)
+                if a is not None:
+                    a.record_stream(s)
+        tail = [s.cuda_stream]
+    pointers = [address(a) if a is not None else None for a in [pixels] + outs]
+    if not getattr(lib, device if on_device else host)(view, *pointers, n, *([] if flags is None else [flags]), *tail):
+        raise RuntimeError(lib.last_error())
+    outs = [a for a in outs if a is not None]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def camera_rays(lib, view, pixels=None, count=None, differentials=True, stream=None):
+    """RT64_GenerateViewCameraRays: the camera rays the view's last frame traced for `pixels` -- an (N, 2) uint32 array of (x, y), or None with `count`: the frame's
+    first `count` pixels row by row -- as (N, 8) float32 RT64_RAYs (that frame's jitter included, direction not normalised, tMin 0.1, tMax 100000) and, with
+    `differentials`, their (N, 16) float32 RT64_RAY_DIFFERENTIALs: dOdx xyz, reserved, dOdy xyz, reserved, dDdx xyz, reserved, dDdy xyz, reserved (rules F1-F3).
+    Returns rays, or (rays, diffs).  A NumPy array takes the host path; a torch CUDA tensor the device path, enqueued on `stream` like trace_rays."""
+    return _pixel_query(lib, view, "GenerateViewCameraRays", "GenerateViewCameraRaysDevice", pixels, count, [8, 16 if differentials else None], None, stream)
+
+
+def footprint_hits(lib, view, rays, diffs, hits, stream=None):
+    """RT64_FootprintViewRayHits: (N, 8) float32 rays, their (N, 16) float32 differentials (None: all 0, what a frame's secondary rays carry) and the (N, 8) float32
+    hits a trace returned for them -> (N, 16) float32 RT64_RAY_FOOTPRINTs: duvdx xy, duvdy xy, lod, lodNormal, lodSpecular, flags, dPdx xyz, instance, dPdy xyz,
+    primitive (flags, instance, primitive as uint32 / int32 bits: read them through `.view(int32)`): the UV gradients and the clamped mip levels the frame's
+    surface any-hit program uses for the hit (rules F4-F8).  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    return _query(lib, view, "FootprintViewRayHits", "FootprintViewRayHitsDevice", [("in", rays), ("diffs", diffs), ("in", hits), ("out", 16)], None, stream)
+
+
+def trace_pixel_footprints(lib, view, pixels=None, count=None, flags=0):
+    """RT64_TraceViewPixelFootprints on an (N, 2) uint32 NumPy array of pixels (or None with `count`): camera_rays, the walk of trace_rays and footprint_hits in one
+    staging round trip -> (rays (N, 8), hits (N, 8), footprints (N, 16)).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
+    return _pixel_query(lib, view, "TraceViewPixelFootprints", None, pixels, count, [8, 8, 16], flags)
