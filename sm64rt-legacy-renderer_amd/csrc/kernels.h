@@ -4,6 +4,7 @@
 #include "rt64_gpu.h"
 #include "../../include/rt64_lighting.h"     // (includes rt64_alpha.h, rt64_material.h, rt64_surface.h and rt64_query.h)
 #include "../../include/rt64_footprint.h"
+#include "../../include/rt64_bounce.h"
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -180,3 +181,12 @@ hipError_t launch_camera_rays(const FrameParams &P, const void *pixels, uint64_t
 // RT64_FootprintViewRayHits: `count` RT64_RAYs, their RT64_RAY_DIFFERENTIALs (nullptr: all 0) and RT64_RAY_HITs -> RT64_RAY_FOOTPRINTs (device pointers, 16-byte aligned) from the
 // instance and texture tables of P and the vertex and index arrays they point to; no texel is read (rules F4-F8).  Reads neither P.traversalStack nor the LDS scene cache.
 hipError_t launch_hit_footprint(const FrameParams &P, const void *rays, const void *diffs, const void *hits, void *footprints, uint64_t count, hipStream_t s);
+
+// ---- bounce.hip -----------------------------------------------------------------------------------------------------
+// RT64_BounceViewRayHits: `count` RT64_RAYs, their RT64_RAY_HITs and (lods != nullptr) one float lod per record -> RT64_RAY_BOUNCEs, reflected RT64_RAYs and refracted RT64_RAYs
+// (device pointers, 16-byte aligned; lods 4; an output that is nullptr is not written) from the instance and texture tables of P (rules R1-R6).  carryCounters: the records
+// take the hits' traversal counters (the hits come from the walk of the same call), otherwise 0 (R8).  Reads neither P.traversalStack nor the LDS scene cache.
+hipError_t launch_hit_bounce(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *bounces, void *reflected, void *refracted, uint64_t count, bool carryCounters, hipStream_t s);
+// RT64_TraceViewRayMirrorChains: `count` RT64_RAYs and (lods != nullptr) their lods -> depth * count RT64_RAY_HITs and RT64_RAY_BOUNCEs, segment-major (rule R7); 1 <= depth <= 8.
+// P.traversalStack as for launch_ray_query; reads the texture table of P as well.
+hipError_t launch_mirror_chain(const FrameParams &P, const void *rays, const void *lods, void *hits, void *bounces, uint64_t count, uint32_t depth, uint32_t flags, hipStream_t s);

@@ -226,6 +226,7 @@ struct Device {
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
     DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility, queryLighting, queryPixels, queryDiffs, queryFootprints;
+    DevArray<uint8_t> queryBounces, queryReflected, queryRefracted;
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -2385,6 +2386,91 @@ static void run_view_footprint(const char *fn, View *v, const void *pixels, void
     query_finish(fn, dev, v, P, s);
 }
 
+// The calls of include/rt64_bounce.h (bounce.hip; rules R1-R12), beside run_view_query and run_view_footprint: their array sets differ -- three outputs, each optional, and
+// the segment-major arrays of a chain.  BOUNCE_RECORDS: rays + hits (+ lods) -> bounces, reflected, refracted.  With BOUNCE_WALK in front, host arrays only: rays (+ lods) ->
+// RT64_TraceViewRaysAlpha's hits (`hits` an optional output) -> the records (RT64_TraceViewRayBounces).  BOUNCE_CHAIN stands alone: rays (+ lods) -> depth * count hits and
+// bounces, record (s, i) at s * count + i (RT64_TraceViewRayMirrorChains).
+enum : int { BOUNCE_WALK = 1, BOUNCE_RECORDS = 2, BOUNCE_CHAIN = 4 };
+static void run_view_bounce(const char *fn, View *v, const void *rays, void *hits, const void *lods, void *bounces, void *reflected, void *refracted, size_t count, unsigned depth,
+                            unsigned flags, void *stream, bool hostArrays, int work) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool walk = (work & BOUNCE_WALK) != 0, chain = (work & BOUNCE_CHAIN) != 0;
+    if (!v) fail("NULL view.");
+    if (chain) { if (!rays || !hits || !bounces) fail("NULL ray, hit or bounce array."); }
+    else {
+        if (!rays || (!hits && !walk)) fail(walk ? "NULL ray array." : "NULL ray or hit array.");
+        if (!bounces && !reflected && !refracted) fail("all three output arrays are NULL.");          // R10
+    }
+    if (chain && (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING)) fail("unknown flags (a mirror chain takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // R10
+    if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RAY_FLAG_ACCEPT_FIRST_HIT)) fail("unknown flags.");          // K3
+    if (chain && (depth < 1u || depth > (unsigned)RT64_MIRROR_CHAIN_MAX_DEPTH)) fail("depth must be 1 to " + std::to_string(RT64_MIRROR_CHAIN_MAX_DEPTH) + ".");
+    if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(bounces) | reinterpret_cast<uintptr_t>(reflected) |
+                         reinterpret_cast<uintptr_t>(refracted)) & 15u))
+        fail(chain ? "the ray, hit and bounce arrays must be 16-byte aligned." : "the ray, hit, bounce, reflected and refracted arrays must be 16-byte aligned.");
+    if (!hostArrays && (reinterpret_cast<uintptr_t>(lods) & 3u)) fail("the lod array must be 4-byte aligned.");
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    query_frame_check(q, true, true, fail);          // R10: K9's, texture rule included
+    dev->use();
+    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
+    if (count == 0) return;
+    hipStream_t s;
+    const FrameParams P = query_start(dev, v, walk || chain, hostArrays ? nullptr : stream, s);
+    FrameParams R = P; R.traversalStack = nullptr;                    // the resolve kernel: no stack, no slab
+    if (hostArrays) {
+        // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | bounces | reflected | refracted] down as far as
+        // the call wants them.  A chain's chunk of n rays comes down as depth blocks of n records each and is scattered to the caller's segment-major arrays.
+        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), recB = sizeof(RT64_RAY_BOUNCE), lodB = lods ? sizeof(float) : 0;
+        const size_t segs = chain ? depth : 1u;
+        const bool hitsUp = !walk && !chain, hitsDown = (walk && hits) || chain;
+        const size_t upB = rayB + (hitsUp ? hitB : 0) + lodB;
+        const size_t downB = (hitsDown ? hitB * segs : 0) + (bounces ? recB * segs : 0) + (reflected ? rayB : 0) + (refracted ? rayB : 0);
+        const size_t chunk = std::min<size_t>(count, ((size_t)1 << 18) / segs);
+        dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB * segs);
+        if (bounces) dev->queryBounces.reserve(chunk * recB * segs);
+        if (reflected) dev->queryReflected.reserve(chunk * rayB);
+        if (refracted) dev->queryRefracted.reserve(chunk * rayB);
+        if (lods) dev->queryLods.reserve(chunk * lodB);
+        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
+        for (size_t at = 0; at < count; at += chunk) {
+            const size_t n = std::min(chunk, count - at);
+            uint8_t *up = pin;
+            memcpy(up, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
+            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, up, n * rayB, hipMemcpyHostToDevice, s)); up += n * rayB;
+            if (hitsUp) {
+                memcpy(up, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, up, n * hitB, hipMemcpyHostToDevice, s)); up += n * hitB;
+            }
+            if (lods) {
+                memcpy(up, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, up, n * lodB, hipMemcpyHostToDevice, s));
+            }
+            const void *dl = lods ? dev->queryLods.ptr : nullptr;
+            if (chain) HIP_CHECK(launch_mirror_chain(P, dev->queryRays.ptr, dl, dev->queryHits.ptr, dev->queryBounces.ptr, n, depth, flags, s));
+            else {
+                if (walk) HIP_CHECK(launch_alpha_query(P, dev->queryRays.ptr, dl, dev->queryHits.ptr, n, flags, s));
+                HIP_CHECK(launch_hit_bounce(R, dev->queryRays.ptr, dev->queryHits.ptr, dl, bounces ? dev->queryBounces.ptr : nullptr, reflected ? dev->queryReflected.ptr : nullptr,
+                                            refracted ? dev->queryRefracted.ptr : nullptr, n, walk, s));
+            }
+            uint8_t *down = pin, *hitsAt = nullptr, *recAt = nullptr, *reflAt = nullptr, *refrAt = nullptr;
+            if (hitsDown) { hitsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB * segs, hipMemcpyDeviceToHost, s)); down += n * hitB * segs; }
+            if (bounces) { recAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryBounces.ptr, n * recB * segs, hipMemcpyDeviceToHost, s)); down += n * recB * segs; }
+            if (reflected) { reflAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryReflected.ptr, n * rayB, hipMemcpyDeviceToHost, s)); down += n * rayB; }
+            if (refracted) { refrAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryRefracted.ptr, n * rayB, hipMemcpyDeviceToHost, s)); }
+            HIP_CHECK(hipStreamSynchronize(s));
+            for (size_t k = 0; k < segs; k++) {          // segment k of the chunk -> segment k of the call
+                if (hitsAt) memcpy(static_cast<uint8_t *>(hits) + (k * count + at) * hitB, hitsAt + k * n * hitB, n * hitB);
+                if (recAt) memcpy(static_cast<uint8_t *>(bounces) + (k * count + at) * recB, recAt + k * n * recB, n * recB);
+            }
+            if (reflAt) memcpy(static_cast<uint8_t *>(reflected) + at * rayB, reflAt, n * rayB);
+            if (refrAt) memcpy(static_cast<uint8_t *>(refracted) + at * rayB, refrAt, n * rayB);
+        }
+    }
+    else if (chain) HIP_CHECK(launch_mirror_chain(P, rays, lods, hits, bounces, count, depth, flags, s));
+    else HIP_CHECK(launch_hit_bounce(R, rays, hits, lods, bounces, reflected, refracted, count, false, s));
+    query_finish(fn, dev, v, P, s);
+}
+
 }  // namespace rt64
 
 // ======================================================================================================================================
@@ -2599,6 +2685,22 @@ RT64_EXPORT int RT64_FootprintViewRayHitsDevice(RT64_VIEW *view, const void *ray
 }
 RT64_EXPORT int RT64_TraceViewPixelFootprints(RT64_VIEW *view, const unsigned int *pixels, RT64_RAY *rays, RT64_RAY_HIT *hits, RT64_RAY_FOOTPRINT *footprints, size_t count, unsigned int flags) {
     RT64_TRY run_view_footprint("RT64_TraceViewPixelFootprints", reinterpret_cast<View *>(view), pixels, rays, nullptr, hits, footprints, count, flags, nullptr, true, FOOTPRINT_GENERATE | FOOTPRINT_WALK | FOOTPRINT_RECORDS); return 1; RT64_CATCH(0)
+}
+// include/rt64_bounce.h (rules R1-R12; the const casts only fit the shared signature: the resolve forms do not write hits)
+RT64_EXPORT int RT64_BounceViewRayHits(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, RT64_RAY_BOUNCE *bounces, RT64_RAY *reflected, RT64_RAY *refracted, size_t count) {
+    RT64_TRY run_view_bounce("RT64_BounceViewRayHits", reinterpret_cast<View *>(view), rays, const_cast<RT64_RAY_HIT *>(hits), lods, bounces, reflected, refracted, count, 0, 0, nullptr, true, BOUNCE_RECORDS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_BounceViewRayHitsDevice(RT64_VIEW *view, const void *rays, const void *hits, const void *lods, void *bounces, void *reflected, void *refracted, size_t count, void *stream) {
+    RT64_TRY run_view_bounce("RT64_BounceViewRayHitsDevice", reinterpret_cast<View *>(view), rays, const_cast<void *>(hits), lods, bounces, reflected, refracted, count, 0, 0, stream, false, BOUNCE_RECORDS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayBounces(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, RT64_RAY_BOUNCE *bounces, RT64_RAY *reflected, RT64_RAY *refracted, size_t count, unsigned int flags) {
+    RT64_TRY run_view_bounce("RT64_TraceViewRayBounces", reinterpret_cast<View *>(view), rays, hits, lods, bounces, reflected, refracted, count, 0, flags, nullptr, true, BOUNCE_WALK | BOUNCE_RECORDS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayMirrorChains(RT64_VIEW *view, const RT64_RAY *rays, const float *lods, unsigned int depth, RT64_RAY_HIT *hits, RT64_RAY_BOUNCE *bounces, size_t count, unsigned int flags) {
+    RT64_TRY run_view_bounce("RT64_TraceViewRayMirrorChains", reinterpret_cast<View *>(view), rays, hits, lods, bounces, nullptr, nullptr, count, depth, flags, nullptr, true, BOUNCE_CHAIN); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayMirrorChainsDevice(RT64_VIEW *view, const void *rays, const void *lods, unsigned int depth, void *hits, void *bounces, size_t count, unsigned int flags, void *stream) {
+    RT64_TRY run_view_bounce("RT64_TraceViewRayMirrorChainsDevice", reinterpret_cast<View *>(view), rays, hits, lods, bounces, nullptr, nullptr, count, depth, flags, stream, false, BOUNCE_CHAIN); return 1; RT64_CATCH(0)
 }
 
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {

@@ -267,6 +267,16 @@ FOOTPRINT_API = [
     ("TraceViewPixelFootprints", "RT64_TraceViewPixelFootprints", C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
 ]
 FOOTPRINT_VALID, FOOTPRINT_BAD_HIT, FOOTPRINT_HAS_UV, FOOTPRINT_TEXTURED = 0x01, 0x02, 0x04, 0x08
+# include/rt64_bounce.h: the frame's mirror and glass rays for hits, mirror chains (rules R1-R12), a list and a loader (RT64_LoadLibraryBounce) of its own
+BOUNCE_API = [
+    ("BounceViewRayHits", "RT64_BounceViewRayHits", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t]),
+    ("BounceViewRayHitsDevice", "RT64_BounceViewRayHitsDevice", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewRayBounces", "RT64_TraceViewRayBounces", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+    ("TraceViewRayMirrorChains", "RT64_TraceViewRayMirrorChains", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, C.c_size_t, C.c_uint]),
+    ("TraceViewRayMirrorChainsDevice", "RT64_TraceViewRayMirrorChainsDevice", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, C.c_size_t, C.c_uint, _P]),
+]
+(BOUNCE_VALID, BOUNCE_BAD_HIT, BOUNCE_BACK_FACE, BOUNCE_MIRROR, BOUNCE_GLASS, BOUNCE_TOTAL_INTERNAL, BOUNCE_CONTINUED) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
+MIRROR_CHAIN_MAX_DEPTH = 8
 
 
 class RAY(C.Structure):
@@ -308,7 +318,12 @@ class RAY_FOOTPRINT(C.Structure):
                 ("flags", C.c_uint), ("dPdx", C.c_float * 3), ("instance", C.c_int), ("dPdy", C.c_float * 3), ("primitive", C.c_uint)]
 
 
-assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64
+class RAY_BOUNCE(C.Structure):
+    _fields_ = [("fresnel", C.c_float), ("reflectionFactor", C.c_float), ("refractionFactor", C.c_float), ("flags", C.c_uint),
+                ("instance", C.c_int), ("primitive", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
+
+
+assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64 and C.sizeof(RAY_BOUNCE) == 32
 assert C.sizeof(RAY_DIFFERENTIAL) == 64 and C.sizeof(RAY_FOOTPRINT) == 64
 assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
 
@@ -335,7 +350,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API + BOUNCE_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -351,10 +366,22 @@ def exported_symbols():
     return [s for _, s, _, _ in API + EXT_API]
 
 
+class _Scalar:
+    """An argument of a query entry point that is a plain number between its arrays (_query's kind "value")."""
+    def __init__(self, value):
+        self.value = value
+
+
+def _out_shape(n, width):
+    """(N, width), or (segments, N, width) for a width given as (segments, width): a chain's segment-major records."""
+    return (width[0], n, width[1]) if isinstance(width, tuple) else (n, width)
+
+
 def _query(lib, view, host, device, args, flags=None, stream=None):
     """The call behind every ray-query wrapper.  `args` lists the entry point's array arguments in its order as (kind, value) pairs: ("in", an (N, 8)
     float32 array: rays, hits), ("lods", an (N,) float32 array, or None for NULL), ("diffs", an (N, 16) float32 array of RT64_RAY_DIFFERENTIALs, or None for
-    NULL), ("out", the width of an (N, width) float32 array to allocate).
+    NULL), ("out", the width of an (N, width) float32 array to allocate -- None: NULL, nothing is returned for it; (S, width): an (S, N, width) array), ("value", a
+    number passed as it is).
     NumPy inputs go to the entry point `host`; torch tensors to `device` (None: the call has no device form), enqueued on `stream`.  Behind the
     arrays go count, flags (unless None) and the stream.  Returns the outputs in order; raises ValueError for a wrong array,
     RuntimeError(RT64_GetLastError) on a refusal."""
@@ -375,7 +402,7 @@ def _query(lib, view, host, device, args, flags=None, stream=None):
             raise ValueError("diffs: an (N, 16) float32 CUDA tensor")
         ins, lods = [a.contiguous() for a in ins], lods.contiguous() if lods is not None else None
         diffs = diffs.contiguous() if diffs is not None else None
-        new = lambda width: torch.empty((ins[0].shape[0], width), dtype=torch.float32, device=ins[0].device)
+        new = lambda width: torch.empty(_out_shape(ins[0].shape[0], width), dtype=torch.float32, device=ins[0].device)
         address = lambda a: a.data_ptr()
     else:
         import numpy as np
@@ -390,20 +417,21 @@ def _query(lib, view, host, device, args, flags=None, stream=None):
             diffs = np.ascontiguousarray(diffs, dtype=np.float32)
             if diffs.shape != (ins[0].shape[0], 16):
                 raise ValueError("diffs: an (N, 16) float32 array")
-        new = lambda width: np.empty((ins[0].shape[0], width), dtype=np.float32)
+        new = lambda width: np.empty(_out_shape(ins[0].shape[0], width), dtype=np.float32)
         address = lambda a: a.ctypes.data
     checked = iter(ins)
-    arrays = [next(checked) if kind == "in" else lods if kind == "lods" else diffs if kind == "diffs" else new(v) for kind, v in args]          # the entry point's arrays, in its order
-    outs = [a for (kind, _), a in zip(args, arrays) if kind == "out"]
+    arrays = [next(checked) if kind == "in" else lods if kind == "lods" else diffs if kind == "diffs" else _Scalar(v) if kind == "value" else new(v) if v is not None else None
+              for kind, v in args]          # the entry point's arguments in front of count, in its order
+    outs = [a for (kind, _), a in zip(args, arrays) if kind == "out" and a is not None]
     tail = []
     if on_device:
         s = stream if stream is not None else torch.cuda.current_stream(ins[0].device)
         if s != torch.cuda.current_stream(ins[0].device):
             for a in arrays:          # (the allocator must not hand the memory out again before the query has run)
-                if a is not None:
+                if a is not None and not isinstance(a, _Scalar):
                     a.record_stream(s)
         tail = [s.cuda_stream]
-    pointers = [address(a) if a is not None else None for a in arrays]
+    pointers = [a.value if isinstance(a, _Scalar) else address(a) if a is not None else None for a in arrays]
     if not getattr(lib, device if on_device else host)(view, *pointers, ins[0].shape[0], *([] if flags is None else [flags]), *tail):
         raise RuntimeError(lib.last_error())
     return outs[0] if len(outs) == 1 else tuple(outs)
@@ -541,3 +569,29 @@ def trace_pixel_footprints(lib, view, pixels=None, count=None, flags=0):
     """RT64_TraceViewPixelFootprints on an (N, 2) uint32 NumPy array of pixels (or None with `count`): camera_rays, the walk of trace_rays and footprint_hits in one
     staging round trip -> (rays (N, 8), hits (N, 8), footprints (N, 16)).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
     return _pixel_query(lib, view, "TraceViewPixelFootprints", None, pixels, count, [8, 8, 16], flags)
+
+
+def bounce_view_ray_hits(lib, view, rays, hits, lods=None, bounces=True, reflected=True, refracted=True, stream=None):
+    """RT64_BounceViewRayHits: (N, 8) float32 rays, the (N, 8) float32 hits a trace returned for them and, optionally, (N,) float32 lods (None: level 0 for every
+    record) -> (N, 8) float32 RT64_RAY_BOUNCEs (fresnel, reflectionFactor, refractionFactor, then flags, instance, primitive, nodesVisited, trianglesTested as uint32 /
+    int32 bits: read them through `.view(int32)`), the (N, 8) reflected RT64_RAYs and the (N, 8) refracted RT64_RAYs: the rays a frame's reflection and refraction
+    passes cast from each hit (rules R1-R6).  `bounces`, `reflected`, `refracted` = False passes NULL for that output and leaves it out of the result; not all three.
+    NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    return _query(lib, view, "BounceViewRayHits", "BounceViewRayHitsDevice",
+                  [("in", rays), ("in", hits), ("lods", lods), ("out", 8 if bounces else None), ("out", 8 if reflected else None), ("out", 8 if refracted else None)], None, stream)
+
+
+def trace_view_ray_bounces(lib, view, rays, lods=None, flags=0, bounces=True, reflected=True, refracted=True):
+    """RT64_TraceViewRayBounces on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): the walk of trace_rays_alpha and the records of
+    bounce_view_ray_hits in one staging round trip -> (hits (N, 8), bounces (N, 8), reflected (N, 8), refracted (N, 8)), without the outputs switched off."""
+    return _query(lib, view, "TraceViewRayBounces", None,
+                  [("in", rays), ("out", 8), ("lods", lods), ("out", 8 if bounces else None), ("out", 8 if reflected else None), ("out", 8 if refracted else None)], flags)
+
+
+def trace_view_ray_mirror_chains(lib, view, rays, depth, lods=None, flags=0, stream=None):
+    """RT64_TraceViewRayMirrorChains: (N, 8) float32 rays and, optionally, (N,) float32 lods -> (hits (depth, N, 8), bounces (depth, N, 8)): segment 0 is the walk of
+    trace_rays_alpha, every later segment the walk of the previous segment's reflected ray at lod 0 while the hit is a mirror (rule R7); 1 <= depth <= 8.  `flags`:
+    RAY_FLAG_CULL_BACK_FACING only.  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    depth = int(depth)
+    return _query(lib, view, "TraceViewRayMirrorChains", "TraceViewRayMirrorChainsDevice",
+                  [("in", rays), ("lods", lods), ("value", depth), ("out", (max(depth, 0), 8)), ("out", (max(depth, 0), 8))], flags, stream)

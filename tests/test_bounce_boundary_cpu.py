@@ -1,0 +1,105 @@
+"""CPU-only checks of the boundary of the bounce calls (include/rt64_bounce.h): the header compiles on its own, after rt64.h and after all seven other headers,
+as C11 and C++17, the record is 32 bytes with the documented offsets and flag values, and librt64.so / the Python binding carry exactly the names of
+RT64_BOUNCE_API_LIST -- in a list of their own, not in any other *_API or exported_symbols(), and in no other header."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+import __graft_entry__ as graft
+
+ROOT = graft.ROOT
+HEADER = os.path.join(ROOT, "include", "rt64_bounce.h")
+NAMES = ["RT64_BounceViewRayHits", "RT64_BounceViewRayHitsDevice", "RT64_TraceViewRayBounces", "RT64_TraceViewRayMirrorChains", "RT64_TraceViewRayMirrorChainsDevice"]
+FIELDS = ("fresnel", "reflectionFactor", "refractionFactor", "flags", "instance", "primitive", "nodesVisited", "trianglesTested")
+OFFSETS = [0, 4, 8, 12, 16, 20, 24, 28]
+FLAGS = [("VALID", 0x01), ("BAD_HIT", 0x02), ("BACK_FACE", 0x04), ("MIRROR", 0x08), ("GLASS", 0x10), ("TOTAL_INTERNAL", 0x20), ("CONTINUED", 0x40)]
+OTHER_HEADERS = ("rt64.h", "rt64_query.h", "rt64_surface.h", "rt64_material.h", "rt64_alpha.h", "rt64_lighting.h", "rt64_footprint.h")
+OTHER_WORDS = r"Surface|Resolve|ShadeView|RayMaterial|Alpha|Visibility|LightView|Lighting|Footprint|CameraRays"          # what the other boundary tests search the exports for
+# the other lists as they stand: (header, macro, Python list, number of members)
+OTHER_LISTS = [("rt64_query.h", "RT64_QUERY_API_LIST", "QUERY_API", 3), ("rt64_surface.h", "RT64_SURFACE_API_LIST", "SURFACE_API", 3),
+               ("rt64_material.h", "RT64_MATERIAL_API_LIST", "MATERIAL_API", 3), ("rt64_alpha.h", "RT64_ALPHA_API_LIST", "ALPHA_API", 4),
+               ("rt64_lighting.h", "RT64_LIGHTING_API_LIST", "LIGHTING_API", 3), ("rt64_footprint.h", "RT64_FOOTPRINT_API_LIST", "FOOTPRINT_API", 5)]
+
+
+@pytest.fixture(scope="module")
+def built():
+    lib = os.path.join(graft.PKG_DIR, "librt64.so")
+    if not os.path.exists(lib):
+        graft.build()
+    return lib
+
+
+def _declared(header=HEADER, macro="RT64_BOUNCE_API_LIST"):
+    text = open(header).read()
+    body = re.search(r"#define %s\(X\)(.*?)\n\n" % macro, text, re.S).group(1)
+    return re.findall(r"X\((\w+),\s*(RT64_\w+),", body)
+
+
+PROBE = r"""
+#include <stdio.h>
+%s
+int main(void) {
+    RT64_LIBRARY lib; RT64_LIBRARY_BOUNCE p; RT64_LIBRARY_ALPHA a;
+    lib.handle = 0; p = RT64_LoadLibraryBounce(lib); a = RT64_LoadLibraryAlpha(lib);
+    printf("%%d %%d %%d %%d %%d", (int)sizeof(RT64_RAY_BOUNCE), (int)sizeof(RT64_RAY), (int)sizeof(RT64_RAY_HIT), (int)sizeof(RT64_LIBRARY_BOUNCE) / (int)sizeof(void *),
+           RT64_MIRROR_CHAIN_MAX_DEPTH);
+""" + "".join('    printf(" %%%%d", (int)offsetof(RT64_RAY_BOUNCE, %s));\n' % f for f in FIELDS) + r"""
+    printf("\n%%d %%d %%d %%d %%d %%d", p.BounceViewRayHits == 0, p.BounceViewRayHitsDevice == 0, p.TraceViewRayBounces == 0, p.TraceViewRayMirrorChains == 0,
+           p.TraceViewRayMirrorChainsDevice == 0, a.TraceViewRaysAlpha == 0);
+""" + "".join('    printf(" %%%%d", RT64_BOUNCE_%s);\n' % n for n, _ in FLAGS) + r"""
+    printf("\n");
+    return 0;
+}
+"""
+INCLUDES = {"alone": '#include "rt64_bounce.h"', "after_rt64": '#include "rt64.h"\n#include "rt64_bounce.h"',
+            "after_all": "".join('#include "%s"\n' % h for h in OTHER_HEADERS) + '#include "rt64_bounce.h"'}
+INCLUDES.update({"after_" + h[:-2]: '#include "%s"\n#include "rt64_bounce.h"' % h for h in OTHER_HEADERS[1:]})
+
+
+@pytest.mark.parametrize("includes", sorted(INCLUDES))
+@pytest.mark.parametrize("lang", ["c", "cpp"])
+def test_bounce_header_compiles_and_layouts_match(tmp_path, lang, includes):
+    src = tmp_path / ("probe." + lang)
+    src.write_text(PROBE % INCLUDES[includes])
+    exe = tmp_path / "probe"
+    cc, std = ("gcc", "-std=c11") if lang == "c" else ("g++", "-std=c++17")
+    subprocess.run([cc, std, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe), "-ldl"], check=True)
+    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout.split("\n")
+    assert [int(x) for x in out[0].split()] == [32, 32, 32, 5, 8] + OFFSETS
+    assert [int(x) for x in out[1].split()] == [1] * 6 + [v for _, v in FLAGS]
+
+
+def test_library_exports_the_bounce_list(built):
+    h = C.CDLL(built, mode=C.RTLD_LOCAL)
+    declared = _declared()
+    assert [s for _, s in declared] == NAMES
+    for _, name in declared:
+        assert hasattr(h, name), name
+    exported = subprocess.run(["nm", "-D", "--defined-only", built], stdout=subprocess.PIPE, text=True, check=True).stdout
+    found = sorted(set(re.findall(r"\bRT64_\w*(?:Bounce|MirrorChain)\w*", exported)))
+    assert found == sorted(NAMES)                       # exactly the five: no other export with those words
+    assert not [n for n in NAMES if re.search(OTHER_WORDS, n)]
+
+
+def test_python_binding_matches_the_bounce_list():
+    from sm64rt_legacy_renderer_amd import rt64
+    assert [(m, s) for m, s, _, _ in rt64.BOUNCE_API] == _declared()
+    assert C.sizeof(rt64.RAY_BOUNCE) == 32
+    assert [getattr(rt64.RAY_BOUNCE, f).offset for f in FIELDS] == OFFSETS
+    assert [getattr(rt64, "BOUNCE_" + n) for n, _ in FLAGS] == [v for _, v in FLAGS]
+    assert rt64.MIRROR_CHAIN_MAX_DEPTH == 8
+    # the other lists stay what they are, and the other headers do not name these functions
+    names = set(NAMES)
+    assert not names & set(rt64.exported_symbols())
+    for header, macro, attr, count in OTHER_LISTS:
+        theirs = _declared(os.path.join(ROOT, "include", header), macro)
+        assert len(theirs) == count and [(m, s) for m, s, _, _ in getattr(rt64, attr)] == theirs, header
+        assert not names & set(s for _, s in theirs)
+    for other in OTHER_HEADERS:
+        text = open(os.path.join(ROOT, "include", other)).read()
+        assert not any(n in text for n in NAMES) and "Bounce" not in text and "MirrorChain" not in text, other
+    lib = rt64.Library()
+    assert all(callable(getattr(lib, m)) for m, _ in _declared())
