@@ -5,6 +5,7 @@
 #include "../../include/rt64_lighting.h"     // (includes rt64_alpha.h, rt64_material.h, rt64_surface.h and rt64_query.h)
 #include "../../include/rt64_footprint.h"
 #include "../../include/rt64_bounce.h"
+#include "../../include/rt64_layers.h"
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -190,3 +191,13 @@ hipError_t launch_hit_bounce(const FrameParams &P, const void *rays, const void 
 // RT64_TraceViewRayMirrorChains: `count` RT64_RAYs and (lods != nullptr) their lods -> depth * count RT64_RAY_HITs and RT64_RAY_BOUNCEs, segment-major (rule R7); 1 <= depth <= 8.
 // P.traversalStack as for launch_ray_query; reads the texture table of P as well.
 hipError_t launch_mirror_chain(const FrameParams &P, const void *rays, const void *lods, void *hits, void *bounces, uint64_t count, uint32_t depth, uint32_t flags, hipStream_t s);
+
+// ---- layers.hip -----------------------------------------------------------------------------------------------------
+// RT64_TraceViewRayLayers: `count` RT64_RAYs and (lods != nullptr) their lods -> maxLayers * count RT64_RAY_HITs, layer-major, and `count` RT64_RAY_LAYERS (device pointers,
+// 16-byte aligned; lods 4; rules T1-T6); 1 <= maxLayers <= 16.  slab: ray_layer_slab_bytes() of device memory, 16-byte aligned, that no other launch uses meanwhile (the
+// payloads of the lists while they are built; nothing in it outlives the launch).  P.traversalStack as for launch_ray_query; reads the texture table of P as well.
+size_t ray_layer_slab_bytes();
+hipError_t launch_layer_walk(const FrameParams &P, const void *rays, const void *lods, void *hits, void *layers, void *slab, uint64_t count, uint32_t maxLayers, uint32_t flags, hipStream_t s);
+// RT64_WeighViewRayLayers: `count` RT64_RAYs, their maxLayers * count RT64_RAY_HITs and (lods != nullptr) their lods -> maxLayers * count floats and `count` RT64_RAY_COVERAGEs
+// (device pointers, 16-byte aligned; lods and weights 4; rule T7).  Reads neither P.traversalStack nor the LDS scene cache.
+hipError_t launch_layer_weight(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *weights, void *coverage, uint64_t count, uint32_t maxLayers, hipStream_t s);

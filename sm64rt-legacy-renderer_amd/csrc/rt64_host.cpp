@@ -227,6 +227,7 @@ struct Device {
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
     DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility, queryLighting, queryPixels, queryDiffs, queryFootprints;
     DevArray<uint8_t> queryBounces, queryReflected, queryRefracted;
+    DevArray<uint8_t> queryLayerSlab, queryLayers, queryWeights, queryCoverage;        // layers.hip: the payload slab of the lists being built (it takes turns like querySlab), and the staged outputs
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -2471,6 +2472,88 @@ static void run_view_bounce(const char *fn, View *v, const void *rays, void *hit
     query_finish(fn, dev, v, P, s);
 }
 
+// The calls of include/rt64_layers.h (layers.hip; rules T1-T12), beside run_view_bounce: layer-major arrays of maxLayers * count records.  LAYERS_WALK: rays (+ lods) -> hits
+// and layers.  LAYERS_WEIGH: rays + hits (+ lods) -> weights and coverage.  Both, host arrays only: the walk, then the resolve of its hits on the device (T8).
+// The walk builds its lists' payloads in the device's layer slab, sized for the query launch like the spill slab and sharing its turn-taking: every call that uses either
+// slab waits for the event the previous such call recorded.
+enum : int { LAYERS_WALK = 1, LAYERS_WEIGH = 2 };
+static void run_view_layers(const char *fn, View *v, const void *rays, const void *lods, unsigned maxLayers, void *hits, void *layers, void *weights, void *coverage, size_t count,
+                            unsigned flags, void *stream, bool hostArrays, int work) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool walk = (work & LAYERS_WALK) != 0, weigh = (work & LAYERS_WEIGH) != 0 && (!walk || weights || coverage);
+    if (!v) fail("NULL view.");
+    if (walk) { if (!rays || !hits || !layers) fail("NULL ray, hit or layer array."); }
+    else if (!rays || !hits || !weights || !coverage) fail("NULL ray, hit, weight or coverage array.");
+    if (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING) fail("unknown flags (a layer query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // T1
+    if (maxLayers < 1u || maxLayers > (unsigned)RT64_RAY_LAYERS_MAX) fail("maxLayers must be 1 to " + std::to_string(RT64_RAY_LAYERS_MAX) + ".");
+    if (!hostArrays && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(layers) | reinterpret_cast<uintptr_t>(coverage)) & 15u))
+        fail(walk ? "the ray, hit and layer arrays must be 16-byte aligned." : "the ray, hit and coverage arrays must be 16-byte aligned.");
+    if (!hostArrays && (reinterpret_cast<uintptr_t>(lods) & 3u)) fail("the lod array must be 4-byte aligned.");
+    if (!hostArrays && (reinterpret_cast<uintptr_t>(weights) & 3u)) fail("the weight array must be 4-byte aligned.");
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    query_frame_check(q, true, true, fail);          // T11: K9's, texture rule included
+    dev->use();
+    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
+    if (count == 0) return;
+    hipStream_t s;
+    const FrameParams P = query_start(dev, v, walk, hostArrays ? nullptr : stream, s);
+    FrameParams R = P; R.traversalStack = nullptr;                    // the resolve kernel: no stack, no slab
+    if (walk) {
+        dev->queryLayerSlab.reserve(ray_layer_slab_bytes());
+        if (!P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // (with a spill slab query_start has waited)
+    }
+    if (hostArrays) {
+        // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | layers | weights | coverage] down as far as the
+        // call wants them.  A chunk of n rays comes down as maxLayers blocks of n records each and is scattered to the caller's layer-major arrays.
+        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), recB = sizeof(RT64_RAY_LAYERS), covB = sizeof(RT64_RAY_COVERAGE), wB = sizeof(float), lodB = lods ? sizeof(float) : 0;
+        const size_t L = maxLayers;
+        const size_t upB = rayB + (walk ? 0 : hitB * L) + lodB;
+        const size_t downB = (walk ? hitB * L + recB : 0) + (weigh && weights ? wB * L : 0) + (weigh && coverage ? covB : 0);
+        const size_t chunk = std::min<size_t>(count, std::max<size_t>(((size_t)1 << 18) / L, 1));
+        dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB * L);
+        if (walk) dev->queryLayers.reserve(chunk * recB);
+        if (weigh) { dev->queryWeights.reserve(chunk * wB * L); dev->queryCoverage.reserve(chunk * covB); }
+        if (lods) dev->queryLods.reserve(chunk * lodB);
+        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
+        for (size_t at = 0; at < count; at += chunk) {
+            const size_t n = std::min(chunk, count - at);
+            uint8_t *up = pin;
+            memcpy(up, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
+            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, up, n * rayB, hipMemcpyHostToDevice, s)); up += n * rayB;
+            if (!walk) {
+                for (size_t k = 0; k < L; k++) memcpy(up + k * n * hitB, static_cast<const uint8_t *>(hits) + (k * count + at) * hitB, n * hitB);      // layer k of the call -> layer k of the chunk
+                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, up, n * hitB * L, hipMemcpyHostToDevice, s)); up += n * hitB * L;
+            }
+            if (lods) {
+                memcpy(up, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
+                HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, up, n * lodB, hipMemcpyHostToDevice, s));
+            }
+            const void *dl = lods ? dev->queryLods.ptr : nullptr;
+            if (walk) HIP_CHECK(launch_layer_walk(P, dev->queryRays.ptr, dl, dev->queryHits.ptr, dev->queryLayers.ptr, dev->queryLayerSlab.ptr, n, maxLayers, flags, s));
+            if (weigh) HIP_CHECK(launch_layer_weight(R, dev->queryRays.ptr, dev->queryHits.ptr, dl, dev->queryWeights.ptr, dev->queryCoverage.ptr, n, maxLayers, s));
+            uint8_t *down = pin, *hitsAt = nullptr, *recAt = nullptr, *wAt = nullptr, *covAt = nullptr;
+            if (walk) {
+                hitsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB * L, hipMemcpyDeviceToHost, s)); down += n * hitB * L;
+                recAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryLayers.ptr, n * recB, hipMemcpyDeviceToHost, s)); down += n * recB;
+            }
+            if (weigh && weights) { wAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryWeights.ptr, n * wB * L, hipMemcpyDeviceToHost, s)); down += n * wB * L; }
+            if (weigh && coverage) { covAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryCoverage.ptr, n * covB, hipMemcpyDeviceToHost, s)); }
+            HIP_CHECK(hipStreamSynchronize(s));
+            for (size_t k = 0; k < L; k++) {          // layer k of the chunk -> layer k of the call
+                if (hitsAt) memcpy(static_cast<uint8_t *>(hits) + (k * count + at) * hitB, hitsAt + k * n * hitB, n * hitB);
+                if (wAt) memcpy(static_cast<uint8_t *>(weights) + (k * count + at) * wB, wAt + k * n * wB, n * wB);
+            }
+            if (recAt) memcpy(static_cast<uint8_t *>(layers) + at * recB, recAt, n * recB);
+            if (covAt) memcpy(static_cast<uint8_t *>(coverage) + at * covB, covAt, n * covB);
+        }
+    }
+    else if (walk) HIP_CHECK(launch_layer_walk(P, rays, lods, hits, layers, dev->queryLayerSlab.ptr, count, maxLayers, flags, s));
+    else HIP_CHECK(launch_layer_weight(R, rays, hits, lods, weights, coverage, count, maxLayers, s));
+    if (walk && !P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }      // (with a spill slab query_finish records it)
+    query_finish(fn, dev, v, P, s);
+}
+
 }  // namespace rt64
 
 // ======================================================================================================================================
@@ -2701,6 +2784,20 @@ RT64_EXPORT int RT64_TraceViewRayMirrorChains(RT64_VIEW *view, const RT64_RAY *r
 }
 RT64_EXPORT int RT64_TraceViewRayMirrorChainsDevice(RT64_VIEW *view, const void *rays, const void *lods, unsigned int depth, void *hits, void *bounces, size_t count, unsigned int flags, void *stream) {
     RT64_TRY run_view_bounce("RT64_TraceViewRayMirrorChainsDevice", reinterpret_cast<View *>(view), rays, hits, lods, bounces, nullptr, nullptr, count, depth, flags, stream, false, BOUNCE_CHAIN); return 1; RT64_CATCH(0)
+}
+
+// include/rt64_layers.h (rules T1-T12; the const cast only fits the shared signature: the resolve forms do not write hits)
+RT64_EXPORT int RT64_TraceViewRayLayers(RT64_VIEW *view, const RT64_RAY *rays, const float *lods, unsigned int maxLayers, RT64_RAY_HIT *hits, RT64_RAY_LAYERS *layers, float *weights, RT64_RAY_COVERAGE *coverage, size_t count, unsigned int flags) {
+    RT64_TRY run_view_layers("RT64_TraceViewRayLayers", reinterpret_cast<View *>(view), rays, lods, maxLayers, hits, layers, weights, coverage, count, flags, nullptr, true, LAYERS_WALK | LAYERS_WEIGH); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayLayersDevice(RT64_VIEW *view, const void *rays, const void *lods, unsigned int maxLayers, void *hits, void *layers, size_t count, unsigned int flags, void *stream) {
+    RT64_TRY run_view_layers("RT64_TraceViewRayLayersDevice", reinterpret_cast<View *>(view), rays, lods, maxLayers, hits, layers, nullptr, nullptr, count, flags, stream, false, LAYERS_WALK); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_WeighViewRayLayers(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, unsigned int maxLayers, float *weights, RT64_RAY_COVERAGE *coverage, size_t count) {
+    RT64_TRY run_view_layers("RT64_WeighViewRayLayers", reinterpret_cast<View *>(view), rays, lods, maxLayers, const_cast<RT64_RAY_HIT *>(hits), nullptr, weights, coverage, count, 0, nullptr, true, LAYERS_WEIGH); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_WeighViewRayLayersDevice(RT64_VIEW *view, const void *rays, const void *hits, const void *lods, unsigned int maxLayers, void *weights, void *coverage, size_t count, void *stream) {
+    RT64_TRY run_view_layers("RT64_WeighViewRayLayersDevice", reinterpret_cast<View *>(view), rays, lods, maxLayers, const_cast<void *>(hits), nullptr, weights, coverage, count, 0, stream, false, LAYERS_WEIGH); return 1; RT64_CATCH(0)
 }
 
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {

@@ -277,6 +277,16 @@ BOUNCE_API = [
 ]
 (BOUNCE_VALID, BOUNCE_BAD_HIT, BOUNCE_BACK_FACE, BOUNCE_MIRROR, BOUNCE_GLASS, BOUNCE_TOTAL_INTERNAL, BOUNCE_CONTINUED) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
 MIRROR_CHAIN_MAX_DEPTH = 8
+# include/rt64_layers.h: a ray's sorted hit list and each layer's weight (rules T1-T12), a list and a loader (RT64_LoadLibraryLayers) of its own
+LAYERS_API = [
+    ("TraceViewRayLayers", "RT64_TraceViewRayLayers", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+    ("TraceViewRayLayersDevice", "RT64_TraceViewRayLayersDevice", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, C.c_size_t, C.c_uint, _P]),
+    ("WeighViewRayLayers", "RT64_WeighViewRayLayers", C.c_int, [_P, _P, _P, _P, C.c_uint, _P, _P, C.c_size_t]),
+    ("WeighViewRayLayersDevice", "RT64_WeighViewRayLayersDevice", C.c_int, [_P, _P, _P, _P, C.c_uint, _P, _P, C.c_size_t, _P]),
+]
+LAYERS_VALID, LAYERS_ENDS_OPAQUE, LAYERS_FULL = 0x1, 0x2, 0x4
+COVERAGE_VALID, COVERAGE_COVERED, COVERAGE_GLASS, COVERAGE_BAD_HIT = 0x1, 0x2, 0x4, 0x8
+RAY_LAYERS_MAX = 16
 
 
 class RAY(C.Structure):
@@ -323,6 +333,15 @@ class RAY_BOUNCE(C.Structure):
                 ("instance", C.c_int), ("primitive", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
 
 
+class RAY_LAYERS(C.Structure):
+    _fields_ = [("count", C.c_uint), ("flags", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
+
+
+class RAY_COVERAGE(C.Structure):
+    _fields_ = [("transmittance", C.c_float), ("refraction", C.c_float), ("shaded", C.c_uint), ("flags", C.c_uint)]
+
+
+assert C.sizeof(RAY_LAYERS) == 16 and C.sizeof(RAY_COVERAGE) == 16
 assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64 and C.sizeof(RAY_BOUNCE) == 32
 assert C.sizeof(RAY_DIFFERENTIAL) == 64 and C.sizeof(RAY_FOOTPRINT) == 64
 assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
@@ -350,7 +369,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API + BOUNCE_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -595,3 +614,70 @@ def trace_view_ray_mirror_chains(lib, view, rays, depth, lods=None, flags=0, str
     depth = int(depth)
     return _query(lib, view, "TraceViewRayMirrorChains", "TraceViewRayMirrorChainsDevice",
                   [("in", rays), ("lods", lods), ("value", depth), ("out", (max(depth, 0), 8)), ("out", (max(depth, 0), 8))], flags, stream)
+
+
+def _is_torch(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _as_uint32(a):
+    """The uint32 bits of a float32 output array (NumPy: a view; torch: int32 where the build has no uint32)."""
+    if _is_torch(a):
+        import torch
+        return a.view(getattr(torch, "uint32", torch.int32))
+    import numpy as np
+    return a.view(np.uint32)
+
+
+def _layer_count(max_layers):
+    max_layers = int(max_layers)
+    if not 1 <= max_layers <= RAY_LAYERS_MAX:
+        raise ValueError("max_layers: 1 to %d" % RAY_LAYERS_MAX)
+    return max_layers
+
+
+def weigh_view_ray_layers(lib, view, rays, hits, lods=None, stream=None):
+    """RT64_WeighViewRayLayers: (N, 8) float32 rays, the (L, N, 8) float32 hits trace_view_ray_layers returned for them (1 <= L <= 16, layer-major) and, optionally,
+    (N,) float32 lods -> (weights (L, N) float32, coverage (N, 4)): the share of the picture a frame's resolve gives each layer, and per ray transmittance, refraction
+    (float32) and shaded, flags (uint32 bits: read the array through `.view(uint32)`) -- rule T7.  NumPy arrays take the host path; torch CUDA tensors the device
+    path, enqueued on `stream` like trace_rays."""
+    on_device = _is_torch(rays)
+    if on_device:
+        import torch
+        if not _is_torch(hits) or hits.dim() != 3 or hits.shape[2] != 8 or hits.dtype != torch.float32 or not hits.is_cuda:
+            raise ValueError("hits: an (L, N, 8) float32 CUDA tensor")
+        hits = hits.contiguous()
+        address = hits.data_ptr()
+    else:
+        import numpy as np
+        hits = np.ascontiguousarray(hits, dtype=np.float32)
+        if hits.ndim != 3 or hits.shape[2] != 8:
+            raise ValueError("hits: an (L, N, 8) float32 array")
+        address = hits.ctypes.data
+    layers = _layer_count(hits.shape[0])
+    if hits.shape[1] != rays.shape[0]:
+        raise ValueError("one list of hits per ray")
+    if on_device and stream is not None and stream != torch.cuda.current_stream(hits.device):
+        hits.record_stream(stream)
+    weights, coverage = _query(lib, view, "WeighViewRayLayers", "WeighViewRayLayersDevice",
+                               [("in", rays), ("value", address), ("lods", lods), ("value", layers), ("out", (layers, 1)), ("out", 4)], None, stream)
+    return weights.reshape(layers, -1), coverage
+
+
+def trace_view_ray_layers(lib, view, rays, max_layers, lods=None, flags=0, weights=False, stream=None):
+    """RT64_TraceViewRayLayers: (N, 8) float32 rays and, optionally, (N,) float32 lods -> (hits (L, N, 8) float32, layers (N, 4) uint32) with L = max_layers (1..16):
+    per ray the sorted hit list a frame keeps -- key t - depthBias, cut at its first opaque entry, rules T1-T6 -- layer-major, the entries behind a list's end the miss
+    record; `layers` holds count, flags, nodesVisited, trianglesTested.  With `weights` the result is (hits, layers, weights (L, N), coverage (N, 4)) as
+    weigh_view_ray_layers returns them (T8).  `flags`: RAY_FLAG_CULL_BACK_FACING only.  NumPy arrays take the host path (one staging round trip, weights included); torch
+    CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    L = _layer_count(max_layers)
+    if _is_torch(rays):
+        hits, layers = _query(lib, view, "TraceViewRayLayers", "TraceViewRayLayersDevice", [("in", rays), ("lods", lods), ("value", L), ("out", (L, 8)), ("out", 4)], flags, stream)
+        if not weights:
+            return hits, _as_uint32(layers)
+        return (hits, _as_uint32(layers)) + tuple(weigh_view_ray_layers(lib, view, rays, hits, lods, stream))
+    outs = _query(lib, view, "TraceViewRayLayers", None,
+                  [("in", rays), ("lods", lods), ("value", L), ("out", (L, 8)), ("out", 4), ("out", (L, 1) if weights else None), ("out", 4 if weights else None)], flags)
+    if not weights:
+        return outs[0], _as_uint32(outs[1])
+    return outs[0], _as_uint32(outs[1]), outs[2].reshape(L, -1), outs[3]
