@@ -2,7 +2,11 @@
 
 Reference behaviour restated: rt64_shader.cpp:312-442 (raster vertex + pixel shader, blend state), rt64_view.cpp:1225-1254 (drawInstances),
 :1292-1319 (background pass and gBackground), :1657-1661 (foreground pass).  Coverage is integer arithmetic on both sides, so which pixels
-a triangle touches is compared exactly; colours go through fp32 interpolation + the texture sampler and may differ by one RGBA8 step."""
+a triangle touches is compared exactly; colours go through fp32 interpolation + the texture sampler and may differ by one RGBA8 step.
+
+Both sides here are one algorithm (raster spec S0-S8) written twice, so a mistake in the spec itself passes these tests.  The independent statement of the pass -- coverage
+without a clipper, clip-space barycentrics, the blend through the stored byte, pixel by pixel in float64 -- is tests/raster_rule.py (rules Z1-Z10); the
+kernels are held to it in tests/test_gpu_raster_rule.py and the oracle in tests/test_raster_rule.py."""
 import copy
 
 import numpy as np
