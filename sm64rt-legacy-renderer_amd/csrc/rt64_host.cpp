@@ -20,6 +20,7 @@
 
 #include "kernels.h"
 #include "device_math.h"
+#include "query_staging.h"
 
 #define RT64_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -225,7 +226,7 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits, querySurfaces, queryLods, queryMaterials, queryVisibility, queryLighting, queryPixels, queryDiffs, queryFootprints;
+    DevArray<uint8_t> queryRays, queryHits, queryLods, queryRecords, queryPixels, queryDiffs, queryFootprints;      // queryHits: a walk's hits or visibilities; queryRecords: surfaces, materials or lighting
     DevArray<uint8_t> queryBounces, queryReflected, queryRefracted;
     DevArray<uint8_t> queryLayerSlab, queryLayers, queryWeights, queryCoverage;        // layers.hip: the payload slab of the lists being built (it takes turns like querySlab), and the staged outputs
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
@@ -2179,13 +2180,23 @@ template <class Fail> static void query_frame_check(const View::QueryScene &q, b
     if (textures && q.textureDestroyed) fail("a texture of the view's last frame was destroyed since; draw a frame first.");      // H11
 }
 
-// The parameters and the stream of one query call (count > 0), ordered behind the view's last frame.  slab: the call walks (or lights): it gets the query's spill slab
-// when the scene needs one.  callerStream: the stream of a device-array form, or NULL for the device's own.
-static FrameParams query_start(Device *dev, View *v, bool slab, void *callerStream, hipStream_t &s) {
+// One query call past its refusals: its stream, ordered behind the view's last frame, and its parameters -- P for the kernels that walk, R for those that resolve
+// records (no stack, no slab).  turn: the call uses a slab that queries on different streams take turns on.
+struct QueryCall { FrameParams P, R; hipStream_t s; bool turn; };
+
+// What every run_view_* does between its refusals and its launches; false: count is 0, nothing to do.  slab: the call walks (or lights): it gets the query's spill
+// slab when the scene needs one.  ownSlab: it brings a slab that takes turns like the spill slab (the layer slab).  callerStream: the stream of a device-array
+// form, or NULL for the device's own.
+static bool query_start(const char *fn, View *v, size_t count, bool slab, bool ownSlab, void *callerStream, QueryCall &c) {
+    Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
+    dev->use();
+    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
+    if (count == 0) return false;
     dev->enter();                                // the device's stream is now behind every render stream: behind the last frame
     v->pruneQueryEvents(false);
-    FrameParams P = q.P;
+    FrameParams &P = c.P; hipStream_t &s = c.s;
+    P = q.P;
     P.countTraversal = dev->opt.countTraversal ? 1u : 0u;
     P.tileTiming = nullptr; P.traversalStack = nullptr;
     if (slab && q.needSpill) {         // the walk (the shadow walks of a lighting record) can outgrow its LDS entries: the query's own slab, sized for its launch
@@ -2200,13 +2211,17 @@ static FrameParams query_start(Device *dev, View *v, bool slab, void *callerStre
     }
     s = callerStream ? static_cast<hipStream_t>(callerStream) : dev->stream;
     if (s != dev->stream) { HIP_CHECK(hipEventRecord(dev->queryOrder, dev->stream)); HIP_CHECK(hipStreamWaitEvent(s, dev->queryOrder, 0)); }
-    if (P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slab
-    return P;
+    c.turn = P.traversalStack || ownSlab;
+    if (c.turn && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // queries on different streams take turns on the slabs
+    c.R = P; c.R.traversalStack = nullptr;
+    return true;
 }
 
 // Behind the last launch of a query call: the slab's turn ends; an enqueued call leaves its event with the table slot, any other waits and reports dropped stack entries.
-static void query_finish(const char *fn, Device *dev, View *v, const FrameParams &P, hipStream_t s) {
-    if (P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
+static void query_finish(const char *fn, View *v, const QueryCall &c) {
+    Device *dev = v->scene->device;
+    const hipStream_t s = c.s;
+    if (c.turn) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }
     if (s != dev->stream) {      // enqueued: the slot (and, through Device::awaitQueries, the BLASes and the vertex / index arrays) stay as they are until the query has run
         hipEvent_t done = nullptr;
         HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
@@ -2217,6 +2232,21 @@ static void query_finish(const char *fn, Device *dev, View *v, const FrameParams
     }
     HIP_CHECK(hipStreamSynchronize(s));
     query_overflow_check(dev, fn);
+}
+
+// The host-array form of a query call: its arrays as columns of records, each with the device buffer that stages it (buf NULL: the call has no such column), go
+// through the chunk loop of query_staging.h on stream s -- one round trip per chunk of at most `chunk` records: the up copies, launch(at, n) on the columns' device
+// buffers, the down copies, one stream wait.
+struct QueryColumn { DevArray<uint8_t> *buf; const void *src; void *dst; size_t bytes, blocks = 1; };
+template <class Launch> static void query_stage(Device *dev, hipStream_t s, std::initializer_list<QueryColumn> columns, size_t count, size_t chunk, Launch &&launch) {
+    chunk = std::min(count, chunk);
+    std::vector<StageColumn> cols;
+    for (const QueryColumn &q : columns) if (q.buf) { q.buf->reserve(chunk * q.bytes * q.blocks); cols.push_back(StageColumn{q.src, q.dst, q.buf->ptr, q.bytes, q.blocks}); }
+    uint8_t *pin = static_cast<uint8_t *>(dev->staging(stage_pin_bytes(cols.data(), cols.size(), chunk), 1));
+    stage_chunks(cols.data(), cols.size(), count, chunk, pin,
+                 [&](void *d, const void *p, size_t bytes) { HIP_CHECK(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s)); }, launch,
+                 [&](void *p, const void *d, size_t bytes) { HIP_CHECK(hipMemcpyAsync(p, d, bytes, hipMemcpyDeviceToHost, s)); },
+                 [&] { HIP_CHECK(hipStreamSynchronize(s)); });
 }
 
 // What one call does with its records: the walk (query.hip), the surface records of hits (surface.hip), or both back to back.
@@ -2247,61 +2277,31 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
     query_frame_check(q, true, shade || alpha || visibility || light, fail);
-    dev->use();
-    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
-    if (count == 0) return;
-    hipStream_t s;
-    const FrameParams P = query_start(dev, v, walk || light, hostArrays ? nullptr : stream, s);
-    FrameParams R = P; R.traversalStack = nullptr;                    // the resolve reads the instance table and what it points to: no stack, no slab
-    // the walk of the call, if it has one, on device arrays: rays (+ lods) -> RT64_RAY_HITs, or 16-byte RT64_RAY_VISIBILITYs, in `out`
-    auto launch_walk = [&](const void *r, const void *l, void *out, size_t n) {
-        if (visibility) HIP_CHECK(launch_visibility_query(P, r, out, n, flags, s));
-        else if (alpha) HIP_CHECK(launch_alpha_query(P, r, l, out, n, flags, s));
-        else HIP_CHECK(launch_ray_query(P, r, out, n, flags, s));
+    QueryCall c;
+    if (!query_start(fn, v, count, walk || light, false, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    // The kernels of the call on device arrays: its walk, if it has one: rays (+ lods) -> RT64_RAY_HITs, or 16-byte RT64_RAY_VISIBILITYs, in `h`; then the records of the hits in `h`.
+    auto launch = [&](const void *r, void *h, const void *l, void *out, size_t n) {
+        if (visibility) HIP_CHECK(launch_visibility_query(P, r, h, n, flags, s));
+        else if (alpha) HIP_CHECK(launch_alpha_query(P, r, l, h, n, flags, s));
+        else if (trace) HIP_CHECK(launch_ray_query(P, r, h, n, flags, s));
+        if (light) HIP_CHECK(launch_hit_light(P, r, h, l, out, n, s));
+        else if (shade) HIP_CHECK(launch_hit_material(R, r, h, l, out, n, s));
+        else if (resolve) HIP_CHECK(launch_hit_surface(R, r, h, out, n, s));
     };
     if (hostArrays) {
-        // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | surfaces] down as far as the call wants them.
-        // A walk's records (`hits`: RT64_RAY_HITs, or RT64_RAY_VISIBILITYs from their own device buffer) are made on the device and only come down.
+        // Up [rays | hits | lods] as far as the call brings them, down [hits | records] as far as it wants them.  A walk's records (`hits`: RT64_RAY_HITs or
+        // RT64_RAY_VISIBILITYs) are made on the device and only come down; a walk alone moves 2^20 records per round trip, a call with a resolve 2^18.
         static_assert(sizeof(RT64_RAY_MATERIAL) == sizeof(RT64_RAY_SURFACE) && sizeof(RT64_RAY_LIGHTING) == sizeof(RT64_RAY_SURFACE), "one record size for every kind of resolve");
-        const size_t rayB = sizeof(RT64_RAY), hitB = visibility ? sizeof(RT64_RAY_VISIBILITY) : sizeof(RT64_RAY_HIT), surfB = sizeof(RT64_RAY_SURFACE), lodB = lods ? sizeof(float) : 0;
-        const size_t upB = rayB + (walk ? 0 : hitB) + lodB, downB = ((walk && hits) ? hitB : 0) + (resolve ? surfB : 0);
-        const size_t chunk = std::min<size_t>(count, (size_t)1 << (resolve ? 18 : 20));
-        DevArray<uint8_t> &walked = visibility ? dev->queryVisibility : dev->queryHits;
-        dev->queryRays.reserve(chunk * rayB); walked.reserve(chunk * hitB);
-        DevArray<uint8_t> &records = light ? dev->queryLighting : shade ? dev->queryMaterials : dev->querySurfaces;
-        if (resolve) records.reserve(chunk * surfB);
-        if (lods) dev->queryLods.reserve(chunk * lodB);
-        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
-        for (size_t at = 0; at < count; at += chunk) {
-            const size_t n = std::min(chunk, count - at);
-            memcpy(pin, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
-            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, pin, n * rayB, hipMemcpyHostToDevice, s));
-            if (!walk) {
-                memcpy(pin + n * rayB, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
-                HIP_CHECK(hipMemcpyAsync(walked.ptr, pin + n * rayB, n * hitB, hipMemcpyHostToDevice, s));
-            }
-            if (lods) {
-                uint8_t *at4 = pin + n * (upB - lodB);
-                memcpy(at4, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, at4, n * lodB, hipMemcpyHostToDevice, s));
-            }
-            if (walk) launch_walk(dev->queryRays.ptr, lods ? dev->queryLods.ptr : nullptr, walked.ptr, n);
-            if (light) HIP_CHECK(launch_hit_light(P, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
-            else if (shade) HIP_CHECK(launch_hit_material(R, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, records.ptr, n, s));
-            else if (resolve) HIP_CHECK(launch_hit_surface(R, dev->queryRays.ptr, dev->queryHits.ptr, records.ptr, n, s));
-            uint8_t *down = pin;
-            if (walk && hits) { HIP_CHECK(hipMemcpyAsync(down, walked.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
-            if (resolve) HIP_CHECK(hipMemcpyAsync(down, records.ptr, n * surfB, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            if (walk && hits) memcpy(static_cast<uint8_t *>(hits) + at * hitB, pin, n * hitB);
-            if (resolve) memcpy(static_cast<uint8_t *>(surfaces) + at * surfB, down, n * surfB);
-        }
+        query_stage(dev, s, {{&dev->queryRays, rays, nullptr, sizeof(RT64_RAY)},
+                             {&dev->queryHits, walk ? nullptr : hits, walk ? hits : nullptr, visibility ? sizeof(RT64_RAY_VISIBILITY) : sizeof(RT64_RAY_HIT)},
+                             {lods ? &dev->queryLods : nullptr, lods, nullptr, sizeof(float)},
+                             {resolve ? &dev->queryRecords : nullptr, nullptr, surfaces, sizeof(RT64_RAY_SURFACE)}},
+                    count, (size_t)1 << (resolve ? 18 : 20),
+                    [&](size_t, size_t n) { launch(dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, dev->queryRecords.ptr, n); });
     }
-    else if (walk) launch_walk(rays, lods, hits, count);
-    else if (light) HIP_CHECK(launch_hit_light(P, rays, hits, lods, surfaces, count, s));
-    else if (shade) HIP_CHECK(launch_hit_material(R, rays, hits, lods, surfaces, count, s));
-    else HIP_CHECK(launch_hit_surface(R, rays, hits, surfaces, count, s));
-    query_finish(fn, dev, v, P, s);
+    else launch(rays, hits, lods, surfaces, count);
+    query_finish(fn, v, c);
 }
 
 // The calls of include/rt64_footprint.h (footprint.hip; rules F1-F11), beside run_view_query: their array sets differ -- pixels in, two outputs.
@@ -2327,64 +2327,30 @@ static void run_view_footprint(const char *fn, View *v, const void *pixels, void
     query_frame_check(q, walk || records, records, fail);          // F10: the generate calls read no mesh and no texture
     if (generate && (q.P.width <= 0 || q.P.height <= 0)) fail("the view's last frame traced no instance: it kept no camera to make rays from.");
     if (generate && !pixels && count > (size_t)q.P.width * (size_t)q.P.height) fail("more rays than the frame has pixels (pixels = NULL counts them row by row).");      // F1
-    dev->use();
-    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
-    if (count == 0) return;
-    hipStream_t s;
-    const FrameParams P = query_start(dev, v, walk, hostArrays ? nullptr : stream, s);
-    FrameParams R = P; R.traversalStack = nullptr;                    // the generate and footprint kernels: no stack, no slab
+    QueryCall c;
+    if (!query_start(fn, v, count, walk, false, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    // The kernels of the call on device arrays: pixels (NULL: record i is pixel at + i of the frame) -> rays (+ diffs unless NULL), rays -> hits, rays + diffs (or NULL) + hits -> footprints.
+    auto launch = [&](const void *px, size_t at, void *r, void *d, void *h, void *f, size_t n) {
+        if (generate) HIP_CHECK(launch_camera_rays(R, px, at, r, d, n, s));
+        if (walk) HIP_CHECK(launch_ray_query(P, r, h, n, flags, s));
+        if (records) HIP_CHECK(launch_hit_footprint(R, r, d, h, f, n, s));
+    };
     if (hostArrays) {
-        // One round trip per chunk: [pixels] or [rays | diffs | hits] up, the kernels back to back, [rays | diffs], [footprints] or [rays | hits | footprints] down as far as the call wants them.
-        const size_t pixB = 2 * sizeof(uint32_t), rayB = sizeof(RT64_RAY), difB = sizeof(RT64_RAY_DIFFERENTIAL), hitB = sizeof(RT64_RAY_HIT), recB = sizeof(RT64_RAY_FOOTPRINT);
-        const bool diffsUp = !generate && diffs, diffsDown = generate && !walk && diffs, raysDown = generate && rays, hitsDown = walk && hits;
-        const size_t upB = generate ? (pixels ? pixB : 0) : rayB + (diffsUp ? difB : 0) + hitB;
-        const size_t downB = (raysDown ? rayB : 0) + (diffsDown ? difB : 0) + (hitsDown ? hitB : 0) + (records ? recB : 0);
-        const size_t chunk = std::min<size_t>(count, (size_t)1 << 18);
-        dev->queryRays.reserve(chunk * rayB);
-        if (generate && pixels) dev->queryPixels.reserve(chunk * pixB);
-        if (diffsUp || diffsDown || walk) dev->queryDiffs.reserve(chunk * difB);
-        if (walk || records) dev->queryHits.reserve(chunk * hitB);
-        if (records) dev->queryFootprints.reserve(chunk * recB);
-        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
-        const bool useDiffs = walk || diffsUp;          // the footprint kernel's differential: the one just generated, or the caller's
-        for (size_t at = 0; at < count; at += chunk) {
-            const size_t n = std::min(chunk, count - at);
-            if (generate) {
-                if (pixels) {
-                    memcpy(pin, static_cast<const uint8_t *>(pixels) + at * pixB, n * pixB);
-                    HIP_CHECK(hipMemcpyAsync(dev->queryPixels.ptr, pin, n * pixB, hipMemcpyHostToDevice, s));
-                }
-                // (pixels = NULL: record i of the chunk is pixel at + i of the frame)
-                HIP_CHECK(launch_camera_rays(R, pixels ? dev->queryPixels.ptr : nullptr, at, dev->queryRays.ptr, (walk || diffsDown) ? dev->queryDiffs.ptr : nullptr, n, s));
-            }
-            else {
-                uint8_t *up = pin;
-                memcpy(up, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, up, n * rayB, hipMemcpyHostToDevice, s)); up += n * rayB;
-                if (diffsUp) {
-                    memcpy(up, static_cast<const uint8_t *>(diffs) + at * difB, n * difB);
-                    HIP_CHECK(hipMemcpyAsync(dev->queryDiffs.ptr, up, n * difB, hipMemcpyHostToDevice, s)); up += n * difB;
-                }
-                memcpy(up, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, up, n * hitB, hipMemcpyHostToDevice, s));
-            }
-            if (walk) HIP_CHECK(launch_ray_query(P, dev->queryRays.ptr, dev->queryHits.ptr, n, flags, s));
-            if (records) HIP_CHECK(launch_hit_footprint(R, dev->queryRays.ptr, useDiffs ? dev->queryDiffs.ptr : nullptr, dev->queryHits.ptr, dev->queryFootprints.ptr, n, s));
-            uint8_t *down = pin, *raysAt = nullptr, *diffsAt = nullptr, *hitsAt = nullptr, *recAt = nullptr;
-            if (raysDown) { raysAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryRays.ptr, n * rayB, hipMemcpyDeviceToHost, s)); down += n * rayB; }
-            if (diffsDown) { diffsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryDiffs.ptr, n * difB, hipMemcpyDeviceToHost, s)); down += n * difB; }
-            if (hitsDown) { hitsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB, hipMemcpyDeviceToHost, s)); down += n * hitB; }
-            if (records) { recAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryFootprints.ptr, n * recB, hipMemcpyDeviceToHost, s)); }
-            HIP_CHECK(hipStreamSynchronize(s));
-            if (raysAt) memcpy(static_cast<uint8_t *>(rays) + at * rayB, raysAt, n * rayB);
-            if (diffsAt) memcpy(static_cast<uint8_t *>(diffs) + at * difB, diffsAt, n * difB);
-            if (hitsAt) memcpy(static_cast<uint8_t *>(hits) + at * hitB, hitsAt, n * hitB);
-            if (recAt) memcpy(static_cast<uint8_t *>(footprints) + at * recB, recAt, n * recB);
-        }
+        // Up [pixels] or [rays | diffs | hits], down [rays | diffs], [footprints] or [rays | hits | footprints] as far as the call wants them.  The differentials stay on
+        // the device between the generate and the footprint kernel of the composite call.
+        const bool diffsUp = !generate && diffs, diffsDown = generate && !walk && diffs, useDiffs = walk || diffsUp || diffsDown;
+        query_stage(dev, s, {{generate && pixels ? &dev->queryPixels : nullptr, pixels, nullptr, 2 * sizeof(uint32_t)},
+                             {&dev->queryRays, generate ? nullptr : rays, generate ? rays : nullptr, sizeof(RT64_RAY)},
+                             {useDiffs ? &dev->queryDiffs : nullptr, diffsUp ? diffs : nullptr, diffsDown ? diffs : nullptr, sizeof(RT64_RAY_DIFFERENTIAL)},
+                             {walk || records ? &dev->queryHits : nullptr, generate ? nullptr : hits, walk ? hits : nullptr, sizeof(RT64_RAY_HIT)},
+                             {records ? &dev->queryFootprints : nullptr, nullptr, footprints, sizeof(RT64_RAY_FOOTPRINT)}},
+                    count, (size_t)1 << 18, [&](size_t at, size_t n) {
+                        launch(pixels ? dev->queryPixels.ptr : nullptr, at, dev->queryRays.ptr, useDiffs ? dev->queryDiffs.ptr : nullptr, dev->queryHits.ptr, dev->queryFootprints.ptr, n);
+                    });
     }
-    else if (generate) HIP_CHECK(launch_camera_rays(R, pixels, 0, rays, diffs, count, s));
-    else HIP_CHECK(launch_hit_footprint(R, rays, diffs, hits, footprints, count, s));
-    query_finish(fn, dev, v, P, s);
+    else launch(pixels, 0, rays, diffs, hits, footprints, count);
+    query_finish(fn, v, c);
 }
 
 // The calls of include/rt64_bounce.h (bounce.hip; rules R1-R12), beside run_view_query and run_view_footprint: their array sets differ -- three outputs, each optional, and
@@ -2412,64 +2378,35 @@ static void run_view_bounce(const char *fn, View *v, const void *rays, void *hit
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
     query_frame_check(q, true, true, fail);          // R10: K9's, texture rule included
-    dev->use();
-    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
-    if (count == 0) return;
-    hipStream_t s;
-    const FrameParams P = query_start(dev, v, walk || chain, hostArrays ? nullptr : stream, s);
-    FrameParams R = P; R.traversalStack = nullptr;                    // the resolve kernel: no stack, no slab
-    if (hostArrays) {
-        // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | bounces | reflected | refracted] down as far as
-        // the call wants them.  A chain's chunk of n rays comes down as depth blocks of n records each and is scattered to the caller's segment-major arrays.
-        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), recB = sizeof(RT64_RAY_BOUNCE), lodB = lods ? sizeof(float) : 0;
-        const size_t segs = chain ? depth : 1u;
-        const bool hitsUp = !walk && !chain, hitsDown = (walk && hits) || chain;
-        const size_t upB = rayB + (hitsUp ? hitB : 0) + lodB;
-        const size_t downB = (hitsDown ? hitB * segs : 0) + (bounces ? recB * segs : 0) + (reflected ? rayB : 0) + (refracted ? rayB : 0);
-        const size_t chunk = std::min<size_t>(count, ((size_t)1 << 18) / segs);
-        dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB * segs);
-        if (bounces) dev->queryBounces.reserve(chunk * recB * segs);
-        if (reflected) dev->queryReflected.reserve(chunk * rayB);
-        if (refracted) dev->queryRefracted.reserve(chunk * rayB);
-        if (lods) dev->queryLods.reserve(chunk * lodB);
-        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
-        for (size_t at = 0; at < count; at += chunk) {
-            const size_t n = std::min(chunk, count - at);
-            uint8_t *up = pin;
-            memcpy(up, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
-            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, up, n * rayB, hipMemcpyHostToDevice, s)); up += n * rayB;
-            if (hitsUp) {
-                memcpy(up, static_cast<const uint8_t *>(hits) + at * hitB, n * hitB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, up, n * hitB, hipMemcpyHostToDevice, s)); up += n * hitB;
-            }
-            if (lods) {
-                memcpy(up, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, up, n * lodB, hipMemcpyHostToDevice, s));
-            }
-            const void *dl = lods ? dev->queryLods.ptr : nullptr;
-            if (chain) HIP_CHECK(launch_mirror_chain(P, dev->queryRays.ptr, dl, dev->queryHits.ptr, dev->queryBounces.ptr, n, depth, flags, s));
-            else {
-                if (walk) HIP_CHECK(launch_alpha_query(P, dev->queryRays.ptr, dl, dev->queryHits.ptr, n, flags, s));
-                HIP_CHECK(launch_hit_bounce(R, dev->queryRays.ptr, dev->queryHits.ptr, dl, bounces ? dev->queryBounces.ptr : nullptr, reflected ? dev->queryReflected.ptr : nullptr,
-                                            refracted ? dev->queryRefracted.ptr : nullptr, n, walk, s));
-            }
-            uint8_t *down = pin, *hitsAt = nullptr, *recAt = nullptr, *reflAt = nullptr, *refrAt = nullptr;
-            if (hitsDown) { hitsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB * segs, hipMemcpyDeviceToHost, s)); down += n * hitB * segs; }
-            if (bounces) { recAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryBounces.ptr, n * recB * segs, hipMemcpyDeviceToHost, s)); down += n * recB * segs; }
-            if (reflected) { reflAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryReflected.ptr, n * rayB, hipMemcpyDeviceToHost, s)); down += n * rayB; }
-            if (refracted) { refrAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryRefracted.ptr, n * rayB, hipMemcpyDeviceToHost, s)); }
-            HIP_CHECK(hipStreamSynchronize(s));
-            for (size_t k = 0; k < segs; k++) {          // segment k of the chunk -> segment k of the call
-                if (hitsAt) memcpy(static_cast<uint8_t *>(hits) + (k * count + at) * hitB, hitsAt + k * n * hitB, n * hitB);
-                if (recAt) memcpy(static_cast<uint8_t *>(bounces) + (k * count + at) * recB, recAt + k * n * recB, n * recB);
-            }
-            if (reflAt) memcpy(static_cast<uint8_t *>(reflected) + at * rayB, reflAt, n * rayB);
-            if (refrAt) memcpy(static_cast<uint8_t *>(refracted) + at * rayB, refrAt, n * rayB);
+    QueryCall c;
+    if (!query_start(fn, v, count, walk || chain, false, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    // The kernels of the call on device arrays: a chain in one walk; or the walk, if the call has one, and the records of its hits (outputs NULL or not).
+    auto launch = [&](const void *r, void *h, const void *l, void *b, void *rl, void *rr, size_t n) {
+        if (chain) HIP_CHECK(launch_mirror_chain(P, r, l, h, b, n, depth, flags, s));
+        else {
+            if (walk) HIP_CHECK(launch_alpha_query(P, r, l, h, n, flags, s));
+            HIP_CHECK(launch_hit_bounce(R, r, h, l, b, rl, rr, n, walk, s));
         }
+    };
+    if (hostArrays) {
+        // Up [rays | hits | lods] as far as the call brings them, down [hits | bounces | reflected | refracted] as far as it wants them.  A chain's chunk of n rays comes
+        // down as depth blocks of n records each and is scattered to the caller's segment-major arrays.
+        const size_t segs = chain ? depth : 1u;
+        const bool made = walk || chain;          // the hits are made on the device and only come down
+        query_stage(dev, s, {{&dev->queryRays, rays, nullptr, sizeof(RT64_RAY)},
+                             {&dev->queryHits, made ? nullptr : hits, made ? hits : nullptr, sizeof(RT64_RAY_HIT), segs},
+                             {lods ? &dev->queryLods : nullptr, lods, nullptr, sizeof(float)},
+                             {bounces ? &dev->queryBounces : nullptr, nullptr, bounces, sizeof(RT64_RAY_BOUNCE), segs},
+                             {reflected ? &dev->queryReflected : nullptr, nullptr, reflected, sizeof(RT64_RAY)},
+                             {refracted ? &dev->queryRefracted : nullptr, nullptr, refracted, sizeof(RT64_RAY)}},
+                    count, ((size_t)1 << 18) / segs, [&](size_t, size_t n) {
+                        launch(dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, bounces ? dev->queryBounces.ptr : nullptr,
+                               reflected ? dev->queryReflected.ptr : nullptr, refracted ? dev->queryRefracted.ptr : nullptr, n);
+                    });
     }
-    else if (chain) HIP_CHECK(launch_mirror_chain(P, rays, lods, hits, bounces, count, depth, flags, s));
-    else HIP_CHECK(launch_hit_bounce(R, rays, hits, lods, bounces, reflected, refracted, count, false, s));
-    query_finish(fn, dev, v, P, s);
+    else launch(rays, hits, lods, bounces, reflected, refracted, count);
+    query_finish(fn, v, c);
 }
 
 // The calls of include/rt64_layers.h (layers.hip; rules T1-T12), beside run_view_bounce: layer-major arrays of maxLayers * count records.  LAYERS_WALK: rays (+ lods) -> hits
@@ -2493,65 +2430,31 @@ static void run_view_layers(const char *fn, View *v, const void *rays, const voi
     Device *dev = v->scene->device;
     const View::QueryScene &q = v->query;
     query_frame_check(q, true, true, fail);          // T11: K9's, texture rule included
-    dev->use();
-    query_overflow_check(dev, fn);               // (reported by an earlier query that ran on a caller stream)
-    if (count == 0) return;
-    hipStream_t s;
-    const FrameParams P = query_start(dev, v, walk, hostArrays ? nullptr : stream, s);
-    FrameParams R = P; R.traversalStack = nullptr;                    // the resolve kernel: no stack, no slab
-    if (walk) {
-        dev->queryLayerSlab.reserve(ray_layer_slab_bytes());
-        if (!P.traversalStack && dev->querySlabUsed) HIP_CHECK(hipStreamWaitEvent(s, dev->querySlabDone, 0));      // (with a spill slab query_start has waited)
-    }
+    QueryCall c;
+    if (!query_start(fn, v, count, walk, walk, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    if (walk) dev->queryLayerSlab.reserve(ray_layer_slab_bytes());
+    // The kernels of the call on device arrays: the walk: rays (+ lods) -> hits and layers; the resolve: rays + hits (+ lods) -> weights and coverage.
+    auto launch = [&](const void *r, const void *l, void *h, void *ly, void *w, void *cv, size_t n) {
+        if (walk) HIP_CHECK(launch_layer_walk(P, r, l, h, ly, dev->queryLayerSlab.ptr, n, maxLayers, flags, s));
+        if (weigh) HIP_CHECK(launch_layer_weight(R, r, h, l, w, cv, n, maxLayers, s));
+    };
     if (hostArrays) {
-        // One round trip per chunk: [rays | hits | lods] up as far as the call brings them, the kernels back to back, [hits | layers | weights | coverage] down as far as the
-        // call wants them.  A chunk of n rays comes down as maxLayers blocks of n records each and is scattered to the caller's layer-major arrays.
-        const size_t rayB = sizeof(RT64_RAY), hitB = sizeof(RT64_RAY_HIT), recB = sizeof(RT64_RAY_LAYERS), covB = sizeof(RT64_RAY_COVERAGE), wB = sizeof(float), lodB = lods ? sizeof(float) : 0;
+        // Up [rays | hits | lods] as far as the call brings them, down [hits | layers | weights | coverage] as far as it wants them.  A chunk of n rays goes up and comes
+        // down as maxLayers blocks of n records each, gathered from and scattered to the caller's layer-major arrays.
         const size_t L = maxLayers;
-        const size_t upB = rayB + (walk ? 0 : hitB * L) + lodB;
-        const size_t downB = (walk ? hitB * L + recB : 0) + (weigh && weights ? wB * L : 0) + (weigh && coverage ? covB : 0);
-        const size_t chunk = std::min<size_t>(count, std::max<size_t>(((size_t)1 << 18) / L, 1));
-        dev->queryRays.reserve(chunk * rayB); dev->queryHits.reserve(chunk * hitB * L);
-        if (walk) dev->queryLayers.reserve(chunk * recB);
-        if (weigh) { dev->queryWeights.reserve(chunk * wB * L); dev->queryCoverage.reserve(chunk * covB); }
-        if (lods) dev->queryLods.reserve(chunk * lodB);
-        uint8_t *pin = static_cast<uint8_t *>(dev->staging(chunk * std::max(upB, downB), 1));
-        for (size_t at = 0; at < count; at += chunk) {
-            const size_t n = std::min(chunk, count - at);
-            uint8_t *up = pin;
-            memcpy(up, static_cast<const uint8_t *>(rays) + at * rayB, n * rayB);
-            HIP_CHECK(hipMemcpyAsync(dev->queryRays.ptr, up, n * rayB, hipMemcpyHostToDevice, s)); up += n * rayB;
-            if (!walk) {
-                for (size_t k = 0; k < L; k++) memcpy(up + k * n * hitB, static_cast<const uint8_t *>(hits) + (k * count + at) * hitB, n * hitB);      // layer k of the call -> layer k of the chunk
-                HIP_CHECK(hipMemcpyAsync(dev->queryHits.ptr, up, n * hitB * L, hipMemcpyHostToDevice, s)); up += n * hitB * L;
-            }
-            if (lods) {
-                memcpy(up, static_cast<const uint8_t *>(lods) + at * lodB, n * lodB);
-                HIP_CHECK(hipMemcpyAsync(dev->queryLods.ptr, up, n * lodB, hipMemcpyHostToDevice, s));
-            }
-            const void *dl = lods ? dev->queryLods.ptr : nullptr;
-            if (walk) HIP_CHECK(launch_layer_walk(P, dev->queryRays.ptr, dl, dev->queryHits.ptr, dev->queryLayers.ptr, dev->queryLayerSlab.ptr, n, maxLayers, flags, s));
-            if (weigh) HIP_CHECK(launch_layer_weight(R, dev->queryRays.ptr, dev->queryHits.ptr, dl, dev->queryWeights.ptr, dev->queryCoverage.ptr, n, maxLayers, s));
-            uint8_t *down = pin, *hitsAt = nullptr, *recAt = nullptr, *wAt = nullptr, *covAt = nullptr;
-            if (walk) {
-                hitsAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryHits.ptr, n * hitB * L, hipMemcpyDeviceToHost, s)); down += n * hitB * L;
-                recAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryLayers.ptr, n * recB, hipMemcpyDeviceToHost, s)); down += n * recB;
-            }
-            if (weigh && weights) { wAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryWeights.ptr, n * wB * L, hipMemcpyDeviceToHost, s)); down += n * wB * L; }
-            if (weigh && coverage) { covAt = down; HIP_CHECK(hipMemcpyAsync(down, dev->queryCoverage.ptr, n * covB, hipMemcpyDeviceToHost, s)); }
-            HIP_CHECK(hipStreamSynchronize(s));
-            for (size_t k = 0; k < L; k++) {          // layer k of the chunk -> layer k of the call
-                if (hitsAt) memcpy(static_cast<uint8_t *>(hits) + (k * count + at) * hitB, hitsAt + k * n * hitB, n * hitB);
-                if (wAt) memcpy(static_cast<uint8_t *>(weights) + (k * count + at) * wB, wAt + k * n * wB, n * wB);
-            }
-            if (recAt) memcpy(static_cast<uint8_t *>(layers) + at * recB, recAt, n * recB);
-            if (covAt) memcpy(static_cast<uint8_t *>(coverage) + at * covB, covAt, n * covB);
-        }
+        query_stage(dev, s, {{&dev->queryRays, rays, nullptr, sizeof(RT64_RAY)},
+                             {&dev->queryHits, walk ? nullptr : hits, walk ? hits : nullptr, sizeof(RT64_RAY_HIT), L},
+                             {lods ? &dev->queryLods : nullptr, lods, nullptr, sizeof(float)},
+                             {walk ? &dev->queryLayers : nullptr, nullptr, layers, sizeof(RT64_RAY_LAYERS)},
+                             {weigh ? &dev->queryWeights : nullptr, nullptr, weights, sizeof(float), L},
+                             {weigh ? &dev->queryCoverage : nullptr, nullptr, coverage, sizeof(RT64_RAY_COVERAGE)}},
+                    count, std::max<size_t>(((size_t)1 << 18) / L, 1), [&](size_t, size_t n) {
+                        launch(dev->queryRays.ptr, lods ? dev->queryLods.ptr : nullptr, dev->queryHits.ptr, dev->queryLayers.ptr, dev->queryWeights.ptr, dev->queryCoverage.ptr, n);
+                    });
     }
-    else if (walk) HIP_CHECK(launch_layer_walk(P, rays, lods, hits, layers, dev->queryLayerSlab.ptr, count, maxLayers, flags, s));
-    else HIP_CHECK(launch_layer_weight(R, rays, hits, lods, weights, coverage, count, maxLayers, s));
-    if (walk && !P.traversalStack) { HIP_CHECK(hipEventRecord(dev->querySlabDone, s)); dev->querySlabUsed = true; }      // (with a spill slab query_finish records it)
-    query_finish(fn, dev, v, P, s);
+    else launch(rays, lods, hits, layers, weights, coverage, count);
+    query_finish(fn, v, c);
 }
 
 }  // namespace rt64

@@ -147,6 +147,72 @@ def test_forms_sizes_and_the_end_of_the_arrays(rt64_lib, sample_data):
         s.close()
 
 
+def _repeated(rays, lods, count, seed):
+    """`count` rays made of the case's rays over and over, the later repetitions shuffled."""
+    rng = np.random.default_rng(seed)
+    order = np.concatenate([np.arange(len(rays))] + [rng.permutation(len(rays)) for _ in range(-(-count // len(rays)) - 1)])[:count]
+    return np.ascontiguousarray(rays[order]), np.ascontiguousarray(lods[order])
+
+
+def _guarded(records, spare=7):
+    return np.full((records + spare, 8), 0xABABABAB, dtype=np.uint32)
+
+
+def test_host_chains_that_cross_a_chunk_agree_with_the_device_form(rt64_lib, sample_data):
+    """2b.  A host chain of depth 8 stages 2^18 / 8 = 32768 rays per round trip and scatters each chunk's eight blocks to the caller's segment-major arrays: 65 rays
+    more than a chunk, with lods, equal the device form -- which does not chunk -- bit for bit, and the spare records behind both arrays keep their guard words."""
+    name, depth, count = "mapped mirrors", 8, 32768 + 65
+    data, seed, options, flags = BC.make_case(sample_data, name)
+    rays, lods = BC.rays_and_lods(data, name, seed, options)
+    many, many_lods = _repeated(rays, lods, count, 16)
+    s = _open(rt64_lib, data, options)
+    hip = ray_rule.Hip()
+    try:
+        s.draw()
+        d_rays, d_lods, d_hits, d_rec = hip.upload(many), hip.upload(many_lods), hip.alloc(depth * count * 32), hip.alloc(depth * count * 32)
+        assert rt64_lib.TraceViewRayMirrorChainsDevice(s.view, d_rays, d_lods, depth, d_hits, d_rec, count, flags & CULL, None) == 1, rt64_lib.last_error()
+        want = [hip.download(d, np.empty((depth * count, 8), dtype=np.uint32)) for d in (d_hits, d_rec)]
+        assert ((want[1].reshape(depth, count, 8)[1, :, 3] & R.VALID) != 0).sum() >= 32          # chains that go on behind segment 0
+        host = [_guarded(depth * count), _guarded(depth * count)]
+        assert rt64_lib.TraceViewRayMirrorChains(s.view, many.ctypes.data, many_lods.ctypes.data, depth, host[0].ctypes.data, host[1].ctypes.data, count, flags & CULL) == 1, rt64_lib.last_error()
+        for out, w in zip(host, want):
+            assert np.array_equal(out[:len(w)], w) and (out[len(w):] == 0xABABABAB).all()
+    finally:
+        hip.close()
+        s.close()
+
+
+def test_a_host_walk_with_records_that_crosses_a_chunk_is_the_two_device_calls(rt64_lib, sample_data):
+    """2c.  RT64_TraceViewRayBounces (host arrays only) at 2^18 + 65 rays, one chunk and 65: with all four outputs, and with `reflected` alone (hits = NULL: the walk's
+    hits never leave the device), it equals RT64_TraceViewRaysAlphaDevice followed by RT64_BounceViewRayHitsDevice bit for bit; the spare records behind every
+    array keep their guard words."""
+    name, count = "mapped mirrors", (1 << 18) + 65
+    data, seed, options, flags = BC.make_case(sample_data, name)
+    rays, lods = BC.rays_and_lods(data, name, seed, options)
+    many, many_lods = _repeated(rays, lods, count, 17)
+    s = _open(rt64_lib, data, options)
+    hip = ray_rule.Hip()
+    try:
+        s.draw()
+        d_rays, d_lods = hip.upload(many), hip.upload(many_lods)
+        d_out = [hip.alloc(count * 32) for _ in range(4)]          # hits, bounces, reflected, refracted
+        assert rt64_lib.TraceViewRaysAlphaDevice(s.view, d_rays, d_lods, d_out[0], count, flags, None) == 1, rt64_lib.last_error()
+        assert rt64_lib.BounceViewRayHitsDevice(s.view, d_rays, d_out[0], d_lods, d_out[1], d_out[2], d_out[3], count, None) == 1, rt64_lib.last_error()
+        want = [hip.download(d, np.empty((count, 8), dtype=np.uint32)) for d in d_out]
+        assert (want[1][:, 4] != 0xFFFFFFFF).sum() > count // 100 and want[2].any()          # real hits with rays reflected off them
+        host = [_guarded(count) for _ in range(4)]
+        rp, lp = many.ctypes.data, many_lods.ctypes.data
+        assert rt64_lib.TraceViewRayBounces(s.view, rp, host[0].ctypes.data, lp, host[1].ctypes.data, host[2].ctypes.data, host[3].ctypes.data, count, flags) == 1, rt64_lib.last_error()
+        for out, w in zip(host, want):
+            assert np.array_equal(out[:count], w) and (out[count:] == 0xABABABAB).all()
+        alone = _guarded(count)
+        assert rt64_lib.TraceViewRayBounces(s.view, rp, None, lp, None, alone.ctypes.data, None, count, flags) == 1, rt64_lib.last_error()
+        assert np.array_equal(alone[:count], want[2]) and (alone[count:] == 0xABABABAB).all()
+    finally:
+        hip.close()
+        s.close()
+
+
 def test_uniform_and_mixed_waves_give_the_same_records(rt64_lib, sample_data):
     """3.  lighting_cases' 66 instances: the hits sorted by instance (waves of 64 hits that share one: the scalar read of the instance) and the same hits shuffled
     (mixed waves: the per-lane gather), and a batch that starts with waves made of one hit of each of 64 different instances, give the same record for the same hit."""

@@ -253,6 +253,41 @@ def test_sizes_grid_stride_and_the_ends_of_the_arrays(rt64_lib, sample_data):
         s.close()
 
 
+@pytest.mark.parametrize("m, count", [(16, 16384 + 65), (3, 87381 + 1)])
+def test_host_arrays_that_cross_a_chunk_agree_with_the_device_form(rt64_lib, sample_data, m, count):
+    """5b.  The host forms stage 2^18 / maxLayers rays per round trip: 16384 at 16 layers, 87381 (no power of two) at 3.  One ray more than a chunk (65 more at 16
+    layers): RT64_TraceViewRayLayers with weights and coverage, and RT64_WeighViewRayLayers fed with the device walk's hits (the layer-major gather on the way up),
+    equal the device forms -- which do not chunk -- bit for bit on the same rays, and the spare records behind each host array keep their guard words."""
+    data, K, _ = LC.case(sample_data, "instances_8")
+    s = _open(rt64_lib, data)
+    hip = ray_rule.Hip()
+    try:
+        s.draw()
+        rays = LC.rays_of(K, 29)
+        rng = np.random.default_rng(7)
+        order = np.concatenate([np.arange(len(rays))] + [rng.permutation(len(rays)) for _ in range(-(-count // len(rays)) - 1)])[:count]
+        many = np.ascontiguousarray(rays[order])
+        shapes = [(m * count, 8), (count, 4), (m * count,), (count, 4)]
+        d_rays = hip.upload(many)
+        bufs = [hip.alloc(4 * int(np.prod(sh))) for sh in shapes]
+        assert rt64_lib.TraceViewRayLayersDevice(s.view, d_rays, None, m, bufs[0], bufs[1], count, 0, None) == 1, rt64_lib.last_error()
+        assert rt64_lib.WeighViewRayLayersDevice(s.view, d_rays, bufs[0], None, m, bufs[2], bufs[3], count, None) == 1, rt64_lib.last_error()
+        want = [hip.download(b, np.empty(sh, dtype=np.uint32)) for b, sh in zip(bufs, shapes)]
+        assert (want[1][:, 0] >= 2).sum() >= 32 and len(np.unique(want[2])) > 2          # lists with layers behind the first, weights that differ
+        spare = [(sh[0] + 7,) + sh[1:] for sh in shapes]
+        host = [np.full(sh, GUARD, dtype=np.uint32) for sh in spare]
+        assert rt64_lib.TraceViewRayLayers(s.view, many.ctypes.data, None, m, host[0].ctypes.data, host[1].ctypes.data, host[2].ctypes.data, host[3].ctypes.data, count, 0) == 1, rt64_lib.last_error()
+        for out, w in zip(host, want):
+            assert np.array_equal(out[:len(w)], w) and (out[len(w):] == GUARD).all(), (m, w.shape)
+        weighed = [np.full(sh, GUARD, dtype=np.uint32) for sh in spare[2:]]
+        assert rt64_lib.WeighViewRayLayers(s.view, many.ctypes.data, want[0].ctypes.data, None, m, weighed[0].ctypes.data, weighed[1].ctypes.data, count) == 1, rt64_lib.last_error()
+        for out, w in zip(weighed, want[2:]):
+            assert np.array_equal(out[:len(w)], w) and (out[len(w):] == GUARD).all(), (m, w.shape)
+    finally:
+        hip.close()
+        s.close()
+
+
 def test_counters_follow_count_traversal(rt64_lib, sample_data):
     """6.  T6: RT64_RAY_LAYERS' counters are 0 without count_traversal; with it non-zero for the rays that were walked into the scene and 0 for Q6-invalid rays; the
     layers' own counters stay 0."""
