@@ -6,6 +6,7 @@
 #include "../../include/rt64_footprint.h"
 #include "../../include/rt64_bounce.h"
 #include "../../include/rt64_layers.h"
+#include "../../include/rt64_radiance.h"
 
 // ---- lbvh.hip ---------------------------------------------------------------------------------------------------
 #define LBVH_SMALL_MAX 4096u          // leaves handled by the single-workgroup LDS builder
@@ -201,3 +202,14 @@ hipError_t launch_layer_walk(const FrameParams &P, const void *rays, const void 
 // RT64_WeighViewRayLayers: `count` RT64_RAYs, their maxLayers * count RT64_RAY_HITs and (lods != nullptr) their lods -> maxLayers * count floats and `count` RT64_RAY_COVERAGEs
 // (device pointers, 16-byte aligned; lods and weights 4; rule T7).  Reads neither P.traversalStack nor the LDS scene cache.
 hipError_t launch_layer_weight(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *weights, void *coverage, uint64_t count, uint32_t maxLayers, hipStream_t s);
+
+// ---- radiance.hip ---------------------------------------------------------------------------------------------------
+// RT64_SkyViewRays: `count` RT64_RAYs -> RT64_RAY_SKYs (device pointers, 16-byte aligned; rule W1).  Reads P, the sky texture of P's texture table, its tiled copy and
+// the frame's background image; no mesh, no stack.
+hipError_t launch_ray_sky(const FrameParams &P, const void *rays, void *sky, uint64_t count, hipStream_t s);
+// RT64_SkyViewPixels: `count` pixels as launch_camera_rays takes them (nullptr: record i is pixel firstPixel + i of the frame) -> RT64_RAY_SKYs (rule W2).
+hipError_t launch_pixel_sky(const FrameParams &P, const void *pixels, uint64_t firstPixel, void *sky, uint64_t count, hipStream_t s);
+// RT64_ComposeViewRayRadiance: `count` RT64_RAYs, their maxLayers * count RT64_RAY_HITs, layer-major, and (lods != nullptr) their lods -> RT64_RAY_RADIANCEs (device pointers,
+// 16-byte aligned; lods 4; rules W3-W7); 1 <= maxLayers <= 16.  flags: RT64_RADIANCE_FLAG_*.  One shadow walk per admitted light of the lit layer unless UNSHADOWED:
+// P.traversalStack as for launch_ray_query.
+hipError_t launch_ray_radiance(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *radiance, uint64_t count, uint32_t maxLayers, uint32_t flags, hipStream_t s);

@@ -457,6 +457,8 @@ struct View {
         std::vector<std::pair<Mesh *, uint32_t>> meshes;      // the meshes the frame traced and the version (RT64_SetMesh count) it traced
         std::vector<Instance *> instances;                    // TLAS build position -> handle
         std::vector<std::pair<Texture *, uint32_t>> textures;     // the textures of the frame's table and their serials (an address alone does not identify a texture)
+        std::pair<Texture *, uint32_t> sky = { nullptr, 0u }; bool skyDestroyed = false;      // the frame's sky texture, and RT64_DestroyTexture on it (the calls of rt64_radiance.h: W10)
+        bool viewBuffersRead = false;             // a call of rt64_radiance.h was enqueued on a caller stream: it reads `background` and `skyTiled`, which belong to the view, not to a table slot
     } query;
     void snapshotQueryScene();
     void pruneQueryEvents(bool wait);             // forget the completed query events of every slot (wait: host-wait for the others first)
@@ -1169,6 +1171,7 @@ static void host_build_tlas(const GpuInstance *inst, const float (*meshMin)[3], 
 void View::update() {                          // View::update, rt64_view.cpp:1053-1178
     Device *dev = scene->device;
     discardPrologue();                         // (nothing is left from a frame that threw half-way; Device::draw has discarded it already)
+    if (query.viewBuffersRead) { pruneQueryEvents(true); query.viewBuffersRead = false; }      // the frame rewrites (or reallocates) the background image and the sky's tiled copy: it waits for the queries that read them
     {   // View::createOutputBuffers: render size = lround(screen * resolutionScale) (rt64_view.cpp:138-139)
         const float scale = resolutionScale > 0.0f ? resolutionScale : 1.0f;
         int rw = std::max(1, (int)lroundf((float)dev->width * scale)), rh = std::max(1, (int)lroundf((float)dev->height * scale));
@@ -2140,6 +2143,7 @@ static size_t readback(Device *dev, int image, void *dst, size_t dstBytes, bool 
 // The tables of the frame just drawn: what queries walk until the next frame.
 void View::snapshotQueryScene() {
     query.valid = true; query.meshDestroyed = false; query.textureDestroyed = false; query.slot = tabCur; query.needSpill = needSpillSlab;
+    query.skyDestroyed = false; query.sky = { skyPlane, skyPlane ? skyPlane->serial : 0u };
     query.meshes.clear(); query.instances.clear(); query.textures.clear();
     auto holds = [&](Texture *t) { if (t && (query.textures.empty() || query.textures.back().first != t)) query.textures.emplace_back(t, t->serial); };
     for (const RenderInstance &ri : rtInstances) {
@@ -2457,6 +2461,65 @@ static void run_view_layers(const char *fn, View *v, const void *rays, const voi
     query_finish(fn, v, c);
 }
 
+// The calls of include/rt64_radiance.h (radiance.hip; rules W1-W12), beside run_view_layers.  RADIANCE_SKY: rays -> sky records; RADIANCE_SKY with RADIANCE_PIXELS: pixels
+// (or NULL) -> sky records, `rays` holding the pixels.  RADIANCE_RESOLVE: rays + maxLayers * count hits (+ lods) -> radiance records.  With RADIANCE_WALK in front, host arrays
+// only: the walk of run_view_layers, then the resolve of its hits on the device, `hits` and `layers` optional outputs (W8).
+enum : int { RADIANCE_SKY = 1, RADIANCE_PIXELS = 2, RADIANCE_WALK = 4, RADIANCE_RESOLVE = 8 };
+static void run_view_radiance(const char *fn, View *v, const void *rays, const void *lods, unsigned maxLayers, void *hits, void *layers, void *records, size_t count,
+                              unsigned flags, void *stream, bool hostArrays, int work) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool sky = (work & RADIANCE_SKY) != 0, pixels = (work & RADIANCE_PIXELS) != 0, walk = (work & RADIANCE_WALK) != 0;
+    if (!v) fail("NULL view.");
+    if (sky) { if ((!rays && !pixels) || !records) fail(pixels ? "NULL sky array." : "NULL ray or sky array."); }
+    else if (!rays || (!hits && !walk) || !records) fail(walk ? "NULL ray or radiance array." : "NULL ray, hit or radiance array.");
+    if (flags & ~(unsigned)(RT64_RAY_FLAG_CULL_BACK_FACING | RT64_RADIANCE_FLAG_UNSHADOWED | RT64_RADIANCE_FLAG_FOG_FROM_CAMERA))
+        fail("unknown flags (a radiance query takes RT64_RAY_FLAG_CULL_BACK_FACING, RT64_RADIANCE_FLAG_UNSHADOWED and RT64_RADIANCE_FLAG_FOG_FROM_CAMERA only).");      // W9
+    if (!sky && (maxLayers < 1u || maxLayers > (unsigned)RT64_RAY_LAYERS_MAX)) fail("maxLayers must be 1 to " + std::to_string(RT64_RAY_LAYERS_MAX) + ".");
+    if (!hostArrays) {
+        if (pixels) { if ((reinterpret_cast<uintptr_t>(rays) & 7u) || (reinterpret_cast<uintptr_t>(records) & 15u)) fail("the pixel array must be 8-byte aligned, the sky array 16-byte aligned."); }
+        else if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(records)) & 15u)
+            fail(sky ? "the ray and sky arrays must be 16-byte aligned." : "the ray, hit and radiance arrays must be 16-byte aligned.");
+        if (reinterpret_cast<uintptr_t>(lods) & 3u) fail("the lod array must be 4-byte aligned.");
+    }
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    query_frame_check(q, !sky, !sky, fail);          // W10: K9's; the sky calls read no mesh and no surface texture
+    if (q.skyDestroyed) fail("the sky texture of the view's last frame was destroyed since; draw a frame first.");
+    if (q.P.width <= 0 || q.P.height <= 0) fail("the view's last frame traced no instance: it kept no sky to show.");
+    if (pixels && !rays && count > (size_t)q.P.width * (size_t)q.P.height) fail("more records than the frame has pixels (pixels = NULL counts them row by row).");      // F1
+    const bool shadows = !sky && !(flags & RT64_RADIANCE_FLAG_UNSHADOWED);
+    QueryCall c;
+    if (!query_start(fn, v, count, walk || shadows, walk, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    if (walk) dev->queryLayerSlab.reserve(ray_layer_slab_bytes());
+    // The kernels of the call on device arrays: the sky of rays or of pixels (NULL: record i is pixel at + i of the frame); or the walk, if the call has one, and the resolve.
+    auto launch = [&](const void *r, size_t at, const void *l, void *h, void *ly, void *out, size_t n) {
+        if (pixels) HIP_CHECK(launch_pixel_sky(R, r, at, out, n, s));
+        else if (sky) HIP_CHECK(launch_ray_sky(R, r, out, n, s));
+        else {
+            if (walk) HIP_CHECK(launch_layer_walk(P, r, l, h, ly, dev->queryLayerSlab.ptr, n, maxLayers, flags & RT64_RAY_FLAG_CULL_BACK_FACING, s));
+            HIP_CHECK(launch_ray_radiance(shadows ? P : R, r, h, l, out, n, maxLayers, flags, s));
+        }
+    };
+    if (hostArrays) {
+        // Up [rays or pixels | hits | lods] as far as the call brings them, down [hits | layers | records] as far as it wants them; a chunk's hits travel as maxLayers blocks
+        // like run_view_layers'.  The walk's hits and layer records stay on the device unless the caller asked for them.
+        const size_t L = sky ? 1u : maxLayers;
+        query_stage(dev, s, {{pixels ? (rays ? &dev->queryPixels : nullptr) : &dev->queryRays, rays, nullptr, pixels ? 2 * sizeof(uint32_t) : sizeof(RT64_RAY)},
+                             {sky ? nullptr : &dev->queryHits, walk ? nullptr : hits, walk ? hits : nullptr, sizeof(RT64_RAY_HIT), L},
+                             {lods ? &dev->queryLods : nullptr, lods, nullptr, sizeof(float)},
+                             {walk ? &dev->queryLayers : nullptr, nullptr, layers, sizeof(RT64_RAY_LAYERS)},
+                             {&dev->queryRecords, nullptr, records, sky ? sizeof(RT64_RAY_SKY) : sizeof(RT64_RAY_RADIANCE)}},
+                    count, std::max<size_t>(((size_t)1 << 18) / L, 1), [&](size_t at, size_t n) {
+                        launch(pixels ? (rays ? dev->queryPixels.ptr : nullptr) : dev->queryRays.ptr, at, lods ? dev->queryLods.ptr : nullptr, dev->queryHits.ptr, dev->queryLayers.ptr,
+                               dev->queryRecords.ptr, n);
+                    });
+    }
+    else launch(rays, 0, lods, hits, layers, records, count);
+    if (s != dev->stream) v->query.viewBuffersRead = true;
+    query_finish(fn, v, c);
+}
+
 }  // namespace rt64
 
 // ======================================================================================================================================
@@ -2703,6 +2766,28 @@ RT64_EXPORT int RT64_WeighViewRayLayersDevice(RT64_VIEW *view, const void *rays,
     RT64_TRY run_view_layers("RT64_WeighViewRayLayersDevice", reinterpret_cast<View *>(view), rays, lods, maxLayers, const_cast<void *>(hits), nullptr, weights, coverage, count, 0, stream, false, LAYERS_WEIGH); return 1; RT64_CATCH(0)
 }
 
+RT64_EXPORT int RT64_SkyViewRays(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_SKY *sky, size_t count) {
+    RT64_TRY run_view_radiance("RT64_SkyViewRays", reinterpret_cast<View *>(view), rays, nullptr, 0, nullptr, nullptr, sky, count, 0, nullptr, true, RADIANCE_SKY); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_SkyViewRaysDevice(RT64_VIEW *view, const void *rays, void *sky, size_t count, void *stream) {
+    RT64_TRY run_view_radiance("RT64_SkyViewRaysDevice", reinterpret_cast<View *>(view), rays, nullptr, 0, nullptr, nullptr, sky, count, 0, stream, false, RADIANCE_SKY); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_SkyViewPixels(RT64_VIEW *view, const unsigned int *pixels, RT64_RAY_SKY *sky, size_t count) {
+    RT64_TRY run_view_radiance("RT64_SkyViewPixels", reinterpret_cast<View *>(view), pixels, nullptr, 0, nullptr, nullptr, sky, count, 0, nullptr, true, RADIANCE_SKY | RADIANCE_PIXELS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_SkyViewPixelsDevice(RT64_VIEW *view, const void *pixels, void *sky, size_t count, void *stream) {
+    RT64_TRY run_view_radiance("RT64_SkyViewPixelsDevice", reinterpret_cast<View *>(view), pixels, nullptr, 0, nullptr, nullptr, sky, count, 0, stream, false, RADIANCE_SKY | RADIANCE_PIXELS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_ComposeViewRayRadiance(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, unsigned int maxLayers, RT64_RAY_RADIANCE *radiance, size_t count, unsigned int flags) {
+    RT64_TRY run_view_radiance("RT64_ComposeViewRayRadiance", reinterpret_cast<View *>(view), rays, lods, maxLayers, const_cast<RT64_RAY_HIT *>(hits), nullptr, radiance, count, flags, nullptr, true, RADIANCE_RESOLVE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_ComposeViewRayRadianceDevice(RT64_VIEW *view, const void *rays, const void *hits, const void *lods, unsigned int maxLayers, void *radiance, size_t count, unsigned int flags, void *stream) {
+    RT64_TRY run_view_radiance("RT64_ComposeViewRayRadianceDevice", reinterpret_cast<View *>(view), rays, lods, maxLayers, const_cast<void *>(hits), nullptr, radiance, count, flags, stream, false, RADIANCE_RESOLVE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayRadiance(RT64_VIEW *view, const RT64_RAY *rays, const float *lods, unsigned int maxLayers, RT64_RAY_HIT *hits, RT64_RAY_LAYERS *layers, RT64_RAY_RADIANCE *radiance, size_t count, unsigned int flags) {
+    RT64_TRY run_view_radiance("RT64_TraceViewRayRadiance", reinterpret_cast<View *>(view), rays, lods, maxLayers, hits, layers, radiance, count, flags, nullptr, true, RADIANCE_WALK | RADIANCE_RESOLVE); return 1; RT64_CATCH(0)
+}
+
 RT64_EXPORT RT64_INSTANCE *RT64_GetViewRaytracedInstance(RT64_VIEW *viewPtr, int instance) {
     const View *v = reinterpret_cast<View *>(viewPtr);
     if (!v || !v->query.valid || instance < 0 || (size_t)instance >= v->query.instances.size()) return nullptr;
@@ -2787,8 +2872,10 @@ RT64_EXPORT void RT64_DestroyTexture(RT64_TEXTURE *texture) {
         Device *dev = t->device;
         dev->enter(); dev->beforeSceneMutation(); hipStreamSynchronize(dev->stream);
         try { dev->awaitQueries(); } catch (...) {}          // a material query on a caller stream may still read the texels (H11)
-        for (Scene *sc : dev->scenes) for (View *v : sc->views)
+        for (Scene *sc : dev->scenes) for (View *v : sc->views) {
             for (auto &e : v->query.textures) if (e.first == t && e.second == t->serial) { v->query.textureDestroyed = true; e.first = nullptr; }
+            if (v->query.sky.first == t && v->query.sky.second == t->serial) { v->query.skyDestroyed = true; v->query.sky.first = nullptr; }
+        }
     }
     delete t;
     RT64_CATCH_VOID

@@ -287,6 +287,19 @@ LAYERS_API = [
 LAYERS_VALID, LAYERS_ENDS_OPAQUE, LAYERS_FULL = 0x1, 0x2, 0x4
 COVERAGE_VALID, COVERAGE_COVERED, COVERAGE_GLASS, COVERAGE_BAD_HIT = 0x1, 0x2, 0x4, 0x8
 RAY_LAYERS_MAX = 16
+# include/rt64_radiance.h: the colour a ray brings back and the sky behind it (rules W1-W12), a list and a loader (RT64_LoadLibraryRadiance) of its own
+RADIANCE_API = [
+    ("SkyViewRays", "RT64_SkyViewRays", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("SkyViewRaysDevice", "RT64_SkyViewRaysDevice", C.c_int, [_P, _P, _P, C.c_size_t, _P]),
+    ("SkyViewPixels", "RT64_SkyViewPixels", C.c_int, [_P, _P, _P, C.c_size_t]),
+    ("SkyViewPixelsDevice", "RT64_SkyViewPixelsDevice", C.c_int, [_P, _P, _P, C.c_size_t, _P]),
+    ("ComposeViewRayRadiance", "RT64_ComposeViewRayRadiance", C.c_int, [_P, _P, _P, _P, C.c_uint, _P, C.c_size_t, C.c_uint]),
+    ("ComposeViewRayRadianceDevice", "RT64_ComposeViewRayRadianceDevice", C.c_int, [_P, _P, _P, _P, C.c_uint, _P, C.c_size_t, C.c_uint, _P]),
+    ("TraceViewRayRadiance", "RT64_TraceViewRayRadiance", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+SKY_VALID, SKY_NO_TEXTURE, SKY_BACKGROUND = 0x1, 0x2, 0x4
+(RADIANCE_VALID, RADIANCE_COVERED, RADIANCE_BAD_HIT, RADIANCE_LIT, RADIANCE_FOGGED, RADIANCE_TRUNCATED) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+RADIANCE_FLAG_UNSHADOWED, RADIANCE_FLAG_FOG_FROM_CAMERA = 0x100, 0x200
 
 
 class RAY(C.Structure):
@@ -341,7 +354,17 @@ class RAY_COVERAGE(C.Structure):
     _fields_ = [("transmittance", C.c_float), ("refraction", C.c_float), ("shaded", C.c_uint), ("flags", C.c_uint)]
 
 
+class RAY_SKY(C.Structure):
+    _fields_ = [("color", C.c_float * 3), ("alpha", C.c_float), ("uv", C.c_float * 2), ("flags", C.c_uint), ("reserved", C.c_uint)]
+
+
+class RAY_RADIANCE(C.Structure):
+    _fields_ = [("radiance", C.c_float * 3), ("flags", C.c_uint), ("surface", C.c_float * 3), ("transmittance", C.c_float),
+                ("transparent", C.c_float * 3), ("litLayer", C.c_int), ("light", C.c_float * 3), ("layers", C.c_uint)]
+
+
 assert C.sizeof(RAY_LAYERS) == 16 and C.sizeof(RAY_COVERAGE) == 16
+assert C.sizeof(RAY_SKY) == 32 and C.sizeof(RAY_RADIANCE) == 64
 assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64 and C.sizeof(RAY_BOUNCE) == 32
 assert C.sizeof(RAY_DIFFERENTIAL) == 64 and C.sizeof(RAY_FOOTPRINT) == 64
 assert C.sizeof(RAY) == 32 and C.sizeof(RAY_HIT) == 32 and C.sizeof(RAY_SURFACE) == 64 and C.sizeof(RAY_MATERIAL) == 64
@@ -369,7 +392,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API + RADIANCE_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -681,3 +704,60 @@ def trace_view_ray_layers(lib, view, rays, max_layers, lods=None, flags=0, weigh
     if not weights:
         return outs[0], _as_uint32(outs[1])
     return outs[0], _as_uint32(outs[1]), outs[2].reshape(L, -1), outs[3]
+
+
+def sky_view_rays(lib, view, rays, stream=None):
+    """RT64_SkyViewRays: (N, 8) float32 rays -> (N, 8) float32 RT64_RAY_SKYs: color rgb, alpha, uv, then flags and reserved as uint32 bits (read them through
+    `.view(uint32)`): what a mirror, glass or GI ray of the view's last frame sees when it misses everything -- the sky texture along the direction as given, over
+    the frame's raster background (rule W1).  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    return _query(lib, view, "SkyViewRays", "SkyViewRaysDevice", [("in", rays), ("out", 8)], None, stream)
+
+
+def sky_view_pixels(lib, view, pixels=None, count=None, stream=None):
+    """RT64_SkyViewPixels: `pixels` as camera_rays takes them -- an (N, 2) uint32 array of (x, y), or None with `count`: the frame's first `count` pixels row by row --
+    -> (N, 8) float32 RT64_RAY_SKYs as sky_view_rays returns them: what a camera ray of the view's last frame shows when it misses everything, the sky plane at
+    screenUV = (p + jitter) / size over the raster background (rule W2).  A NumPy array takes the host path; a torch CUDA tensor the device path, enqueued on `stream`."""
+    return _pixel_query(lib, view, "SkyViewPixels", "SkyViewPixelsDevice", pixels, count, [8], None, stream)
+
+
+def resolve_view_ray_radiance(lib, view, rays, hits, lods=None, flags=0, stream=None):
+    """RT64_ComposeViewRayRadiance: (N, 8) float32 rays, the (L, N, 8) float32 hits trace_view_ray_layers returned for them (1 <= L <= 16, layer-major) and, optionally,
+    (N,) float32 lods -> (N, 16) float32 RT64_RAY_RADIANCEs: radiance rgb, flags, surface rgb, transmittance, transparent rgb, litLayer, light rgb, layers (flags,
+    litLayer, layers as uint32 / int32 bits: read them through `.view(int32)`): the colour the ray brings back in the secondary-ray resolve of the view's last frame
+    (rules W3-W7).  `flags`: RAY_FLAG_CULL_BACK_FACING, RADIANCE_FLAG_UNSHADOWED, RADIANCE_FLAG_FOG_FROM_CAMERA.  NumPy arrays take the host path; torch CUDA tensors
+    the device path, enqueued on `stream` like trace_rays."""
+    on_device = _is_torch(rays)
+    if on_device:
+        import torch
+        if not _is_torch(hits) or hits.dim() != 3 or hits.shape[2] != 8 or hits.dtype != torch.float32 or not hits.is_cuda:
+            raise ValueError("hits: an (L, N, 8) float32 CUDA tensor")
+        hits = hits.contiguous()
+        address = hits.data_ptr()
+    else:
+        import numpy as np
+        hits = np.ascontiguousarray(hits, dtype=np.float32)
+        if hits.ndim != 3 or hits.shape[2] != 8:
+            raise ValueError("hits: an (L, N, 8) float32 array")
+        address = hits.ctypes.data
+    layers = _layer_count(hits.shape[0])
+    if hits.shape[1] != rays.shape[0]:
+        raise ValueError("one list of hits per ray")
+    if on_device and stream is not None and stream != torch.cuda.current_stream(hits.device):
+        hits.record_stream(stream)
+    return _query(lib, view, "ComposeViewRayRadiance", "ComposeViewRayRadianceDevice",
+                  [("in", rays), ("value", address), ("lods", lods), ("value", layers), ("out", 16)], flags, stream)
+
+
+def trace_view_ray_radiance(lib, view, rays, max_layers=RAY_LAYERS_MAX, lods=None, flags=0, hits=True, layers=True):
+    """RT64_TraceViewRayRadiance on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): the walk of trace_view_ray_layers and the records of
+    resolve_view_ray_radiance in one staging round trip -> (hits (L, N, 8), layers (N, 4) uint32, radiance (N, 16)) with L = max_layers; `hits`, `layers` = False
+    passes NULL for that output and leaves it out of the result (rule W8)."""
+    L = _layer_count(max_layers)
+    outs = _query(lib, view, "TraceViewRayRadiance", None,
+                  [("in", rays), ("lods", lods), ("value", L), ("out", (L, 8) if hits else None), ("out", 4 if layers else None), ("out", 16)], flags)
+    if not hits and not layers:
+        return outs
+    outs = list(outs)
+    if layers:
+        outs[1 if hits else 0] = _as_uint32(outs[1 if hits else 0])
+    return tuple(outs)
