@@ -11,7 +11,8 @@ and the scene as the host sent it.  It predicts INDIRECT_LIGHT_RAW (rgb and alph
 
 Reference lines cited as (I:n) are IndirectRayGen.hlsl, (R:n) Random.hlsli, (S:n) BgSky.hlsli, (B:n) BlueNoise.hlsli.
 
-Out of scope: temporal reprojection, the SVGF guide and input folds of the resolve kernel, normal and specular maps at the bounce hit, hit lists past 16
+Temporal reprojection -- frames WITH history -- is held by tests/temporal_rule.py (rules N1-N8), which takes this rule's frame as its fresh sample.
+Out of scope: the SVGF guide and input folds of the resolve kernel, normal and specular maps at the bounce hit, hit lists past 16
 entries, primary_spp > 1.
 """
 import math

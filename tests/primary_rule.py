@@ -13,7 +13,8 @@ The sky behind a pixel is tests/sky_rule.py's (E1-E8) where `scene["sky"]` is a 
 
 Out of scope: normal and
 specular maps and combiners other than mix-colour or TEX0 (H1-H12 hold them); the lod chosen by the primary ray differentials (textures have one level); hit lists past
-16 entries (test_gpu_kbuffer.py); optNoise alpha; primary_spp > 1; the history guides normal[cur] and depth[cur], which have no readback; how a raster background
+16 entries (test_gpu_kbuffer.py); optNoise alpha; primary_spp > 1; what the next frame makes of the history guides normal[cur] and depth[cur] (tests/temporal_rule.py, rules N1-N8, reads them as DEPTH and -- on frames
+without mirrors -- SHADING_NORMAL of the previous frame and holds the temporal accumulation of the GI pass to them); how a raster background
 instance is drawn into IMAGE_BACKGROUND (tests/raster_rule.py, rules Z1-Z10, holds that; tests/test_gpu_raster.py compares it with the oracle's): this rule samples the
 image as stored.  A scene has a constant sky term or a background image, not both; a described sky lies over the background by its alpha (E6).
 """
