@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "rt64_gpu.h"
 #include "../../include/rt64_lighting.h"     // (includes rt64_alpha.h, rt64_material.h, rt64_surface.h and rt64_query.h)
+#include "../../include/rt64_sampled_lighting.h"
 #include "../../include/rt64_footprint.h"
 #include "../../include/rt64_bounce.h"
 #include "../../include/rt64_layers.h"
@@ -175,6 +176,13 @@ hipError_t launch_visibility_query(const FrameParams &P, const void *rays, void 
 // RT64_LightViewRayHits: `count` RT64_RAYs, their RT64_RAY_HITs and (lods != nullptr) one float lod per record -> RT64_RAY_LIGHTINGs (device pointers, 16-byte aligned;
 // lods 4) from the instance, texture and light tables of P, with one shadow walk per admitted light (rules P1-P11).  P.traversalStack as for launch_ray_query.
 hipError_t launch_hit_light(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *lighting, uint64_t count, hipStream_t s);
+
+// ---- sampled_lighting.hip -------------------------------------------------------------------------------------------
+// RT64_SampleViewRayLights: `count` RT64_RAYs, their RT64_RAY_HITs, (lods != nullptr) one float lod and (keys != nullptr) one RT64_LIGHT_SAMPLE_KEY per record ->
+// RT64_RAY_SAMPLED_LIGHTINGs (device pointers, 16-byte aligned; lods 4): the frame's light loop with `maxLights` draws and `diSamples` disc samples, one shadow walk per
+// sample (rules J1-J11).  keys == nullptr: record i is keyed as pixel first + i of the frame, row by row.  P.traversalStack as for launch_ray_query.
+hipError_t launch_hit_sampled_light(const FrameParams &P, const void *rays, const void *hits, const void *lods, const void *keys, uint64_t first, uint32_t maxLights, uint32_t diSamples,
+                                    void *records, uint64_t count, hipStream_t s);
 
 // ---- footprint.hip --------------------------------------------------------------------------------------------------
 // RT64_GenerateViewCameraRays: `count` pixels (x, y pairs of uint32, 8-byte aligned; nullptr: record i is pixel n = firstPixel + i of the frame, (n % P.width, n / P.width), and firstPixel + count <= P.width * P.height) -> the

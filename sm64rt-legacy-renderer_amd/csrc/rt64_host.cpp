@@ -226,7 +226,7 @@ struct Device {
     // Ray queries (RT64_TraceViewRays, query.hip): their own spill slab (sized for the query launch, lane headers pointing at their own overflow word), the event the
     // last launch that used it recorded (queries on different caller streams take turns on it), device buffers + pinned staging of the host-array form
     DevArray<uint32_t> querySlab; uint32_t *queryOverflow = nullptr; hipEvent_t querySlabDone = nullptr, queryOrder = nullptr; bool querySlabUsed = false;
-    DevArray<uint8_t> queryRays, queryHits, queryLods, queryRecords, queryPixels, queryDiffs, queryFootprints;      // queryHits: a walk's hits or visibilities; queryRecords: surfaces, materials or lighting
+    DevArray<uint8_t> queryRays, queryHits, queryLods, queryKeys, queryRecords, queryPixels, queryDiffs, queryFootprints;      // queryHits: a walk's hits or visibilities; queryRecords: surfaces, materials or lighting
     DevArray<uint8_t> queryBounces, queryReflected, queryRefracted;
     DevArray<uint8_t> queryLayerSlab, queryLayers, queryWeights, queryCoverage;        // layers.hip: the payload slab of the lists being built (it takes turns like querySlab), and the staged outputs
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
@@ -2308,6 +2308,53 @@ static void run_view_query(const char *fn, View *v, const void *rays, void *hits
     query_finish(fn, v, c);
 }
 
+// The calls of include/rt64_sampled_lighting.h (sampled_lighting.hip; rules J1-J11), beside run_view_query: QUERY_LIGHT's arrays plus one key per record (or NULL) and
+// the call's sampling parameters, resolved here against the view's last frame and handed to the kernel by value.  walk: RT64_TraceViewRaysAlpha in front, host arrays
+// only, `hits` an optional output (RT64_TraceViewRaySampledLights).
+static void run_view_sampled_light(const char *fn, View *v, const void *rays, void *hits, const void *lods, const void *keys, const RT64_LIGHT_SAMPLING *sampling, void *records,
+                                   size_t count, unsigned flags, void *stream, bool hostArrays, bool walk) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    if (!v) fail("NULL view.");
+    if (!rays || !records || (!hits && !walk)) fail("NULL ray, hit or record array.");
+    if (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING) fail("unknown flags (a sampled lighting query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // J11
+    if (sampling) {                                                                                                                                                // J4
+        if (sampling->flags != 0u) fail("unknown sampling flags.");
+        if (sampling->maxLights < -1 || sampling->maxLights > RT64_LIGHT_SAMPLING_MAX_LIGHTS) fail("maxLights must be 0 to " + std::to_string(RT64_LIGHT_SAMPLING_MAX_LIGHTS) + ", or -1 for the last frame's.");
+        if (sampling->diSamples < -1 || sampling->diSamples > RT64_LIGHT_SAMPLING_MAX_SAMPLES) fail("diSamples must be 0 to " + std::to_string(RT64_LIGHT_SAMPLING_MAX_SAMPLES) + ", or -1 for the last frame's.");
+    }
+    if (!hostArrays) {
+        if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(records)) & 15u)
+            fail("the ray, hit, key and record arrays must be 16-byte aligned.");
+        if (reinterpret_cast<uintptr_t>(lods) & 3u) fail("the lod array must be 4-byte aligned.");
+    }
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    query_frame_check(q, true, true, fail);
+    if (!keys && count > (size_t)std::max(q.P.width, 0) * (size_t)std::max(q.P.height, 0)) fail("more records than the frame has pixels (keys = NULL counts them row by row).");      // J3
+    const uint32_t maxLights = sampling && sampling->maxLights >= 0 ? (uint32_t)sampling->maxLights : q.P.maxLights;
+    const uint32_t diSamples = sampling && sampling->diSamples >= 0 ? (uint32_t)sampling->diSamples : q.P.diSamples;
+    QueryCall c;
+    if (!query_start(fn, v, count, true, false, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P; const hipStream_t s = c.s;
+    // The kernels of the call on device arrays: the walk, if the call has one, then the records of the hits in `h`; records at .. at + n - 1 of the call.
+    auto launch = [&](const void *r, void *h, const void *l, const void *k, size_t at, void *out, size_t n) {
+        if (walk) HIP_CHECK(launch_alpha_query(P, r, l, h, n, flags, s));
+        HIP_CHECK(launch_hit_sampled_light(P, r, h, l, k, at, maxLights, diSamples, out, n, s));
+    };
+    if (hostArrays) {
+        // Up [rays | hits | lods | keys] as far as the call brings them, down [hits | records] as far as it wants them.
+        query_stage(dev, s, {{&dev->queryRays, rays, nullptr, sizeof(RT64_RAY)},
+                             {&dev->queryHits, walk ? nullptr : hits, walk ? hits : nullptr, sizeof(RT64_RAY_HIT)},
+                             {lods ? &dev->queryLods : nullptr, lods, nullptr, sizeof(float)},
+                             {keys ? &dev->queryKeys : nullptr, keys, nullptr, sizeof(RT64_LIGHT_SAMPLE_KEY)},
+                             {&dev->queryRecords, nullptr, records, sizeof(RT64_RAY_SAMPLED_LIGHTING)}},
+                    count, (size_t)1 << 18,
+                    [&](size_t at, size_t n) { launch(dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, keys ? dev->queryKeys.ptr : nullptr, at, dev->queryRecords.ptr, n); });
+    }
+    else launch(rays, hits, lods, keys, 0, records, count);
+    query_finish(fn, v, c);
+}
+
 // The calls of include/rt64_footprint.h (footprint.hip; rules F1-F11), beside run_view_query: their array sets differ -- pixels in, two outputs.
 // FOOTPRINT_GENERATE: pixels (or NULL) -> rays (+ diffs unless NULL).  FOOTPRINT_RECORDS: rays + diffs (or NULL) + hits -> footprints.  Both with FOOTPRINT_WALK between them,
 // host arrays only: pixels -> rays -> RT64_TraceViewRays' hits -> footprints, `rays` and `hits` optional outputs (RT64_TraceViewPixelFootprints).
@@ -2717,6 +2764,18 @@ RT64_EXPORT int RT64_LightViewRayHitsDevice(RT64_VIEW *view, const void *rays, c
 }
 RT64_EXPORT int RT64_TraceViewRayLighting(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, RT64_RAY_LIGHTING *lighting, size_t count, unsigned int flags) {
     RT64_TRY run_view_query("RT64_TraceViewRayLighting", reinterpret_cast<View *>(view), rays, hits, lighting, count, flags, nullptr, true, QUERY_ALPHA | QUERY_LIGHT, lods); return 1; RT64_CATCH(0)
+}
+// include/rt64_sampled_lighting.h (rules J1-J11)
+RT64_EXPORT int RT64_SampleViewRayLights(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, const RT64_LIGHT_SAMPLE_KEY *keys, const RT64_LIGHT_SAMPLING *sampling,
+                                           RT64_RAY_SAMPLED_LIGHTING *records, size_t count) {
+    RT64_TRY run_view_sampled_light("RT64_SampleViewRayLights", reinterpret_cast<View *>(view), rays, const_cast<RT64_RAY_HIT *>(hits), lods, keys, sampling, records, count, 0, nullptr, true, false); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_SampleViewRayLightsDevice(RT64_VIEW *view, const void *rays, const void *hits, const void *lods, const void *keys, const RT64_LIGHT_SAMPLING *sampling, void *records, size_t count, void *stream) {
+    RT64_TRY run_view_sampled_light("RT64_SampleViewRayLightsDevice", reinterpret_cast<View *>(view), rays, const_cast<void *>(hits), lods, keys, sampling, records, count, 0, stream, false, false); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRaySampledLights(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, const RT64_LIGHT_SAMPLE_KEY *keys, const RT64_LIGHT_SAMPLING *sampling,
+                                                 RT64_RAY_SAMPLED_LIGHTING *records, size_t count, unsigned int flags) {
+    RT64_TRY run_view_sampled_light("RT64_TraceViewRaySampledLights", reinterpret_cast<View *>(view), rays, hits, lods, keys, sampling, records, count, flags, nullptr, true, true); return 1; RT64_CATCH(0)
 }
 // include/rt64_footprint.h (rules F1-F11)
 RT64_EXPORT int RT64_GenerateViewCameraRays(RT64_VIEW *view, const unsigned int *pixels, RT64_RAY *rays, RT64_RAY_DIFFERENTIAL *diffs, size_t count) {

@@ -287,6 +287,14 @@ LAYERS_API = [
 LAYERS_VALID, LAYERS_ENDS_OPAQUE, LAYERS_FULL = 0x1, 0x2, 0x4
 COVERAGE_VALID, COVERAGE_COVERED, COVERAGE_GLASS, COVERAGE_BAD_HIT = 0x1, 0x2, 0x4, 0x8
 RAY_LAYERS_MAX = 16
+# include/rt64_sampled_lighting.h: the direct light of a hit as a frame's pixel samples it (rules J1-J11), a list and a loader (RT64_LoadLibrarySampledLighting) of its own
+SAMPLED_LIGHTING_API = [
+    ("SampleViewRayLights", "RT64_SampleViewRayLights", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t]),
+    ("SampleViewRayLightsDevice", "RT64_SampleViewRayLightsDevice", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewRaySampledLights", "RT64_TraceViewRaySampledLights", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+(SAMPLED_LIGHTING_VALID, SAMPLED_LIGHTING_BAD_HIT, SAMPLED_LIGHTING_BACK_FACE, SAMPLED_LIGHTING_UNLIT, SAMPLED_LIGHTING_TRUNCATED) = 0x01, 0x02, 0x04, 0x08, 0x10
+LIGHT_SAMPLING_MAX_LIGHTS, LIGHT_SAMPLING_MAX_SAMPLES = 16, 64
 # include/rt64_radiance.h: the colour a ray brings back and the sky behind it (rules W1-W12), a list and a loader (RT64_LoadLibraryRadiance) of its own
 RADIANCE_API = [
     ("SkyViewRays", "RT64_SkyViewRays", C.c_int, [_P, _P, _P, C.c_size_t]),
@@ -331,6 +339,20 @@ class RAY_LIGHTING(C.Structure):
                 ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
 
 
+class LIGHT_SAMPLE_KEY(C.Structure):
+    _fields_ = [("x", C.c_uint), ("y", C.c_uint), ("frame", C.c_uint), ("reserved", C.c_uint)]
+
+
+class LIGHT_SAMPLING(C.Structure):
+    _fields_ = [("maxLights", C.c_int), ("diSamples", C.c_int), ("flags", C.c_uint), ("reserved", C.c_uint)]
+
+
+class RAY_SAMPLED_LIGHTING(C.Structure):
+    _fields_ = [("direct", C.c_float * 3), ("flags", C.c_uint), ("unshadowed", C.c_float * 3), ("lightsAdmitted", C.c_uint),
+                ("emitted", C.c_float * 3), ("drawn", C.c_uint), ("instance", C.c_int), ("primitive", C.c_uint),
+                ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
+
+
 class RAY_DIFFERENTIAL(C.Structure):
     _fields_ = [("dOdx", C.c_float * 3), ("reserved0", C.c_uint), ("dOdy", C.c_float * 3), ("reserved1", C.c_uint),
                 ("dDdx", C.c_float * 3), ("reserved2", C.c_uint), ("dDdy", C.c_float * 3), ("reserved3", C.c_uint)]
@@ -364,6 +386,7 @@ class RAY_RADIANCE(C.Structure):
 
 
 assert C.sizeof(RAY_LAYERS) == 16 and C.sizeof(RAY_COVERAGE) == 16
+assert C.sizeof(LIGHT_SAMPLE_KEY) == 16 and C.sizeof(LIGHT_SAMPLING) == 16 and C.sizeof(RAY_SAMPLED_LIGHTING) == 64
 assert C.sizeof(RAY_SKY) == 32 and C.sizeof(RAY_RADIANCE) == 64
 assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64 and C.sizeof(RAY_BOUNCE) == 32
 assert C.sizeof(RAY_DIFFERENTIAL) == 64 and C.sizeof(RAY_FOOTPRINT) == 64
@@ -392,7 +415,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API + RADIANCE_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + SAMPLED_LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API + RADIANCE_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -541,6 +564,65 @@ def trace_lighting(lib, view, rays, lods=None, flags=0):
     """RT64_TraceViewRayLighting on an (N, 8) float32 NumPy array of rays (and optional (N,) float32 lods): the walk of trace_rays_alpha and the
     records of light_hits in one staging round trip -> (hits (N, 8), lighting (N, 16)).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
     return _query(lib, view, "TraceViewRayLighting", None, [("in", rays), ("out", 8), ("lods", lods), ("out", 16)], flags)
+
+
+LIGHT_SAMPLE_KEY_DTYPE = [("x", "<u4"), ("y", "<u4"), ("frame", "<u4"), ("reserved", "<u4")]          # numpy dtypes of the three structs of rt64_sampled_lighting.h
+LIGHT_SAMPLING_DTYPE = [("maxLights", "<i4"), ("diSamples", "<i4"), ("flags", "<u4"), ("reserved", "<u4")]
+RAY_SAMPLED_LIGHTING_DTYPE = [("direct", "<f4", (3,)), ("flags", "<u4"), ("unshadowed", "<f4", (3,)), ("lightsAdmitted", "<u4"), ("emitted", "<f4", (3,)), ("drawn", "<u4"),
+                              ("instance", "<i4"), ("primitive", "<u4"), ("nodesVisited", "<u4"), ("trianglesTested", "<u4")]
+
+
+def _sample_keys(rays, keys, stream):
+    """The keys argument of the sampled-lighting wrappers -> (address or None, the array to keep alive): an (N, 4) uint32 array of RT64_LIGHT_SAMPLE_KEYs (x, y, frame,
+    reserved; a structured array of LIGHT_SAMPLE_KEY_DTYPE as well) of the kind the rays are, or None for NULL."""
+    if keys is None:
+        return None, None
+    n = rays.shape[0] if hasattr(rays, "shape") and len(rays.shape) else -1
+    if type(rays).__module__.split(".")[0] == "torch":
+        import torch
+        if type(keys).__module__.split(".")[0] != "torch" or keys.dim() != 2 or tuple(keys.shape) != (n, 4) or keys.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not keys.is_cuda:
+            raise ValueError("keys: an (N, 4) int32 or uint32 CUDA tensor")
+        keys = keys.contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(keys.device)
+        if s != torch.cuda.current_stream(keys.device):
+            keys.record_stream(s)
+        return keys.data_ptr(), keys
+    import numpy as np
+    keys = np.asarray(keys)
+    if keys.dtype.names is not None:
+        keys = np.ascontiguousarray(keys, dtype=np.dtype(LIGHT_SAMPLE_KEY_DTYPE)).view(np.uint32).reshape(-1, 4)
+    if keys.ndim != 2 or keys.shape != (n, 4) or keys.dtype.kind not in "iu":
+        raise ValueError("keys: an (N, 4) uint32 array")
+    keys = np.ascontiguousarray(keys.astype(np.uint32, copy=False))
+    return keys.ctypes.data, keys
+
+
+def _light_sampling(max_lights, di_samples):
+    """RT64_LIGHT_SAMPLING of the two overrides (-1: the last frame's value) -> (address or None for NULL, the struct to keep alive)."""
+    if max_lights == -1 and di_samples == -1:
+        return None, None
+    s = LIGHT_SAMPLING(int(max_lights), int(di_samples), 0, 0)
+    return C.addressof(s), s
+
+
+def sample_lighting(lib, view, rays, hits, lods=None, keys=None, max_lights=-1, di_samples=-1, stream=None):
+    """RT64_SampleViewRayLights: (N, 8) float32 rays, the (N, 8) float32 hits a trace returned for them, optionally (N,) float32 lods (None: level 0) and (N, 4)
+    uint32 keys (x, y, frame, reserved; None: record i is keyed as pixel i of the last frame, row by row, at its frame count) -> (N, 16) float32
+    RT64_RAY_SAMPLED_LIGHTINGs: direct rgb, flags, unshadowed rgb, lightsAdmitted, emitted rgb, drawn, then instance, primitive, nodesVisited, trianglesTested (the
+    integers as uint32 / int32 bits: read them through `.view(int32)`, or the whole array through `.view(RAY_SAMPLED_LIGHTING_DTYPE)`): the direct light of the view's
+    last frame at each hit as the pixel of the key samples it (rules J1-J11).  `max_lights` (0 .. 16) and `di_samples` (0 .. 64) override the frame's values; -1 keeps
+    them.  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    k, keep_k = _sample_keys(rays, keys, stream)
+    p, keep_p = _light_sampling(max_lights, di_samples)
+    return _query(lib, view, "SampleViewRayLights", "SampleViewRayLightsDevice", [("in", rays), ("in", hits), ("lods", lods), ("value", k), ("value", p), ("out", 16)], None, stream)
+
+
+def trace_sampled_lighting(lib, view, rays, lods=None, keys=None, max_lights=-1, di_samples=-1, flags=0):
+    """RT64_TraceViewRaySampledLights on an (N, 8) float32 NumPy array of rays (optional (N,) float32 lods and (N, 4) uint32 keys): the walk of trace_rays_alpha and
+    the records of sample_lighting in one staging round trip -> (hits (N, 8), records (N, 16)).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
+    k, keep_k = _sample_keys(rays, keys, None)
+    p, keep_p = _light_sampling(max_lights, di_samples)
+    return _query(lib, view, "TraceViewRaySampledLights", None, [("in", rays), ("out", 8), ("lods", lods), ("value", k), ("value", p), ("out", 16)], flags)
 
 
 def _pixel_query(lib, view, host, device, pixels, count, widths, flags=None, stream=None):
