@@ -196,7 +196,9 @@ def test_c3_bounce_traversal_with_wave_refill_matches_plain_walk(rt64_lib, sampl
 
 def test_resolution_scale_resamples_the_render_target_to_the_screen(rt64_lib, sample_data):
     """RT64_VIEW_DESC.resolutionScale (rt64_view.cpp:138-139): every image is lround(screen x scale), PostProcessPS.hlsl resamples the
-    composed output to the screen-size back buffer with the LINEAR/WRAP static sampler.  0.75 (upsample) and 1.5 (supersample)."""
+    composed output to the screen-size back buffer with the LINEAR/WRAP static sampler.  0.75 (upsample) and 1.5 (supersample).
+    This is parity with the oracle, whose resample is the same code; that every back-buffer pixel -- the wrapped taps of all four borders, the half texel, ragged
+    sizes -- lies within a float64 restatement's own bound is shown by tests/test_gpu_post_rule.py."""
     for scale, (rw, rh) in ((0.75, (240, 135)), (1.5, (480, 270))):
         got, ref, st = _render_pair(rt64_lib, sample_data, view_desc=dict(resolution_scale=scale))
         assert (st.width, st.height, st.screenWidth, st.screenHeight) == (rw, rh, W, H)
@@ -209,7 +211,9 @@ def test_resolution_scale_resamples_the_render_target_to_the_screen(rt64_lib, sa
 
 def test_motion_blur_gathers_along_the_flow(rt64_lib, sample_data):
     """PostProcessPS.hlsl:14-33: with motionBlurStrength > 0 the back buffer averages motionBlurSamples taps of the output along the
-    screen-space motion vector.  The camera strafes between frames so that the flow is not zero."""
+    screen-space motion vector.  The camera strafes between frames so that the flow is not zero.
+    The pixel-by-pixel hold of the gather -- the 1e-6 threshold, taps clamped to the screen's edge, 1, 3 and 32 samples, a blur under a resolution scale -- is
+    tests/test_gpu_post_rule.py."""
     data = _variant(sample_data, lambda d: None)
     base = data.view.copy()
 
