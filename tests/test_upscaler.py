@@ -4,7 +4,10 @@ rt64_view.cpp:1273-1281,1584-1618).
 CPU: the quality -> render-size table and jitter phase count against the values rt64_fsr.cpp:98-130 / rt64_upscaler.cpp:11-36 imply, the
 Halton sequence against a pure-Python restatement of rt64_common.h:347-361, and a property of the oracle's upscaler that does not share
 its code: on a static scene the accumulated image approaches the native-resolution render more closely than a bilinear upsample does.
-GPU: jittered primary rays hit exactly what the oracle's do, the upscaled image and the back buffer match the oracle's."""
+GPU: jittered primary rays hit exactly what the oracle's do, the upscaled image and the back buffer match the oracle's.
+What each display pixel of UPSCALED must be -- U1-U8 per pixel, in every quality mode, across restarts, at the frame-count cap, with lock and reactive values, with
+histories that leave the screen -- is held elsewhere, against a float64 rule with a derived bound: tests/upscale_rule.py, tests/test_upscale_rule.py (CPU oracle) and
+tests/test_gpu_upscale_rule.py ("The temporal upscaler against a float64 rule").  The whole-image bars below stay as they are."""
 import ctypes as C
 
 import numpy as np
