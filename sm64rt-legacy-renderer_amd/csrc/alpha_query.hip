@@ -5,15 +5,14 @@
 //   alpha_query_kernel       closest hit among the intersections RT64_ShadeViewRayHits would not flag RT64_MATERIAL_CUTOUT (K2); a cutout neither commits nor
 //                            shortens the ray.  Only a texture-edge instance runs the any-hit: one byte of its combiner, read per candidate, says so.
 //   visibility_query_kernel  trace_shadow (shade.h) without a pixel: 1 minus the shadow alphas of every intersection in the window, 0 at a shadow-opaque instance (K5-K7).
+//                            The walk and its handler are shadow_visibility of query_shading.h, the one the lighting and radiance kernels call per light sample.
 //
 // The instance differs per lane and steers control flow.  The any-hit is reached only by the lanes that hold a candidate in this trip of the walk, on an instance that
 // needs it.  The closest-hit handler gathers its lane's instance record with vector loads (inst_view with a per-lane index, material.hip's form for mixed waves).  The
 // frame's `waterfall` (one scalar pass per distinct instance) was built first: it held 2-6 more VGPRs, and on scenes with texture-edge shaders it ignored accepted
-// candidates on about 2 % of the rays, so it does not ship here.  That is an OPEN DEFECT, not a settled choice: the cause is not explained (DESIGN.md 4 lists what was
-// ruled out), and the visibility handler below -- trace_shadow's own, waterfall included, in a handler that may return false -- is the same construct; it passes its rule
-// on all eight cases, which is evidence, not an explanation.
-#include "query_common.h"
-#include "alpha.h"
+// candidates on about 2 % of the rays, so it does not ship here.  That is an OPEN DEFECT, not a settled choice; the visibility handler is the same construct, and the
+// paragraph on what is and is not known stands once, at shadow_visibility (query_shading.h).
+#include "query_shading.h"
 
 namespace {
 
@@ -59,18 +58,10 @@ __global__ __launch_bounds__(RT_BLOCK) void visibility_query_kernel(FrameParams 
     const uint64_t stride = query_stride();
     for (uint64_t i = query_first(); i < count; i += stride) {
         const QueryRay ray = load_ray(QUERY_IN(rays + i));
-        float visibility = 1.0f; uint32_t flags = 0u;
         TraceCounts cnt; cnt.nodes = 0; cnt.tris = 0;
+        float visibility = 1.0f; uint32_t flags = 0u;
         if (query_ray_valid(ray.o, ray.d, ray.tmin, ray.tmax)) {
-            trace_ray<CACHED>(P, ray.o, ray.d, ray.tmin, ray.tmax, cullBackFaces != 0, stk,
-                              [&](float, float u, float v, uint32_t instance, uint32_t prim, float &, uint32_t instFlags, float) -> bool {
-                                  if (instFlags & GPU_INST_SHADOW_OPAQUE) { visibility = 0.0f; return true; }      // K6
-                                  float sa = 0.0f;
-                                  waterfall(instance, [&](uint32_t k) { sa = shadow_alpha_before_noise(P, inst_view(P, k), prim, u, v); });
-                                  if (sa < 0.0f) return false;
-                                  visibility = fmaxf(visibility - sa, 0.0f);
-                                  return !(visibility > 0.0f);
-                              }, cnt);
+            visibility = shadow_visibility<CACHED>(P, mk3(ray.o[0], ray.o[1], ray.o[2]), mk3(ray.d[0], ray.d[1], ray.d[2]), ray.tmin, ray.tmax, cullBackFaces != 0, stk, cnt);      // K5-K7
             flags = RT64_VISIBILITY_VALID | (visibility > 0.0f ? 0u : (uint32_t)RT64_VISIBILITY_BLOCKED);
         }
         keep_counts(P, cnt);
@@ -88,11 +79,7 @@ hipError_t launch_alpha_query(const FrameParams &P, const void *rays, const void
 }
 
 hipError_t launch_visibility_query(const FrameParams &P, const void *rays, void *visibility, uint64_t count, uint32_t flags, hipStream_t s) {
-    if (!count) return hipSuccess;
-    const dim3 grid = query_grid(count), block(RT_BLOCK);
-    const RT64_RAY *r = static_cast<const RT64_RAY *>(rays); RT64_RAY_VISIBILITY *o = static_cast<RT64_RAY_VISIBILITY *>(visibility);
+    decltype(&visibility_query_kernel<false>) kernels[2] = { visibility_query_kernel<false>, visibility_query_kernel<true> };
     const uint32_t cull = (flags & RT64_RAY_FLAG_CULL_BACK_FACING) ? 1u : 0u;
-    if (P.cacheWords) hipLaunchKernelGGL((visibility_query_kernel<true>), grid, block, (size_t)P.cacheWords * 16, s, P, r, o, count, cull);
-    else hipLaunchKernelGGL((visibility_query_kernel<false>), grid, block, 0, s, P, r, o, count, cull);
-    return hipGetLastError();
+    return launch_cached(kernels, P, count, 0, s, static_cast<const RT64_RAY *>(rays), static_cast<RT64_RAY_VISIBILITY *>(visibility), count, cull);
 }

@@ -187,12 +187,8 @@ hipError_t launch_hit_bounce(const FrameParams &P, const void *rays, const void 
 }
 
 hipError_t launch_mirror_chain(const FrameParams &P, const void *rays, const void *lods, void *hits, void *bounces, uint64_t count, uint32_t depth, uint32_t flags, hipStream_t s) {
-    if (!count) return hipSuccess;
-    const dim3 grid = query_grid(count), block(RT_BLOCK);
-    const RT64_RAY *r = static_cast<const RT64_RAY *>(rays); const float *l = static_cast<const float *>(lods);
-    RT64_RAY_HIT *h = static_cast<RT64_RAY_HIT *>(hits); RT64_RAY_BOUNCE *b = static_cast<RT64_RAY_BOUNCE *>(bounces);
+    decltype(&mirror_chain_kernel<false>) kernels[2] = { mirror_chain_kernel<false>, mirror_chain_kernel<true> };
     const uint32_t cull = (flags & RT64_RAY_FLAG_CULL_BACK_FACING) ? 1u : 0u;
-    if (P.cacheWords) hipLaunchKernelGGL((mirror_chain_kernel<true>), grid, block, (size_t)P.cacheWords * 16, s, P, r, l, h, b, count, depth, cull);
-    else hipLaunchKernelGGL((mirror_chain_kernel<false>), grid, block, 0, s, P, r, l, h, b, count, depth, cull);
-    return hipGetLastError();
+    return launch_cached(kernels, P, count, 0, s, static_cast<const RT64_RAY *>(rays), static_cast<const float *>(lods), static_cast<RT64_RAY_HIT *>(hits),
+                         static_cast<RT64_RAY_BOUNCE *>(bounces), count, depth, cull);
 }

@@ -164,14 +164,10 @@ size_t ray_layer_slab_bytes() {
 }
 
 hipError_t launch_layer_walk(const FrameParams &P, const void *rays, const void *lods, void *hits, void *layers, void *slab, uint64_t count, uint32_t maxLayers, uint32_t flags, hipStream_t s) {
-    if (!count) return hipSuccess;
-    const dim3 grid = query_grid(count), block(RT_BLOCK);
-    const RT64_RAY *r = static_cast<const RT64_RAY *>(rays); const float *l = static_cast<const float *>(lods);
-    RT64_RAY_HIT *h = static_cast<RT64_RAY_HIT *>(hits); RT64_RAY_LAYERS *o = static_cast<RT64_RAY_LAYERS *>(layers); u32x4 *b = static_cast<u32x4 *>(slab);
+    decltype(&layer_walk_kernel<false>) kernels[2] = { layer_walk_kernel<false>, layer_walk_kernel<true> };
     const uint32_t cull = (flags & RT64_RAY_FLAG_CULL_BACK_FACING) ? 1u : 0u;
-    if (P.cacheWords) hipLaunchKernelGGL((layer_walk_kernel<true>), grid, block, (size_t)P.cacheWords * 16, s, P, r, l, h, o, b, count, maxLayers, cull);
-    else hipLaunchKernelGGL((layer_walk_kernel<false>), grid, block, 0, s, P, r, l, h, o, b, count, maxLayers, cull);
-    return hipGetLastError();
+    return launch_cached(kernels, P, count, 0, s, static_cast<const RT64_RAY *>(rays), static_cast<const float *>(lods), static_cast<RT64_RAY_HIT *>(hits),
+                         static_cast<RT64_RAY_LAYERS *>(layers), static_cast<u32x4 *>(slab), count, maxLayers, cull);
 }
 
 hipError_t launch_layer_weight(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *weights, void *coverage, uint64_t count, uint32_t maxLayers, hipStream_t s) {

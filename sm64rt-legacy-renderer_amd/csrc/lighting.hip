@@ -8,51 +8,14 @@
 //   read are used (no combiner colour); the compiler drops the rest of inst_view's loads.
 //   The light loop is uniform in `l`: P.lights + l is a scalar load, admission and the term are per lane, and a lane walks only for a light it admitted.  Nothing is
 //   drawn, so the candidate columns of compute_lights_random (shade.h:646-656) are not needed.
-//   The shadow handler is visibility_query_kernel's, statement for statement (alpha_query.hip; its head comment has the open defect of the `waterfall` form).
-// The arithmetic restates shade.h: light_intensity_simple (:581-589) is called; one light is compute_light (:592-633) with radius 0 and one sample, the visibility
-// kept apart from the term so that `unshadowed` and `direct` come from the same numbers; `emitted` is direct_light_pixel's tail (passes.hip:299-304).
-#include "query_common.h"
-#include "alpha.h"
+//   The shaded point, the eye light, the light sample and the shadow walk are query_shading.h's (point_of_hit, eye_light, light_sample, sample_visibility): one copy
+//   for this kernel, hit_sampled_light_kernel and ray_radiance_kernel; the walk is visibility_query_kernel's own (shadow_visibility has the open defect of its
+//   `waterfall` handler).  What is this file's is the miss record, the admission loop and the record.
+// The arithmetic is shade.h's: light_intensity_simple (:581-589) is called; one light is compute_light (:592-633) with radius 0 and one sample (samplePosition = the
+// light's position, rs = 1), the visibility kept apart from the term so that `unshadowed` and `direct` come from the same numbers.
+#include "query_shading.h"
 
 namespace {
-
-struct LightPoint { f3 position, normal, specular, selfLight; float ignoreNormalFactor, shadowRayBias, specularExponent; uint32_t mask, flags; };
-
-// P2 and the material fields of P4-P7 for one real hit of instance `in`: surface_of_hit's position, material_of_hit's normal chain and specular texel
-DEV void point_of_hit(PRef P, const InstView &in, uint32_t prim, float u, float v, f3 rayDirW, float lod, LightPoint &r) {
-    const GpuCombiner &cc = in.cc;
-    const RT64_MATERIAL &mat = in.material;
-    const bool normalMap = (in.flags & GPU_INST_NORMAL_MAP) != 0, specularMap = (in.flags & GPU_INST_SPECULAR_MAP) != 0;
-    const float b[3] = { 1.0f - u - v, u, v };
-    VertexData vd;
-    get_vertex_data(in, prim, b, cc.vertexUV && normalMap, vd);
-    r.flags = RT64_LIGHTING_VALID;
-    r.position = mul_point(in.objectToWorld.m, vd.vertexPosition);                          // A4
-    f3 vertexNormal = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexNormal));    // H8
-    const bool back = dot3(vd.triangleNormal, rayDirW) > 0.0f;
-    const float normalSign = back ? -1.0f : 1.0f;
-    if (back) r.flags |= RT64_LIGHTING_BACK_FACE;
-    vertexNormal = vertexNormal * normalSign;
-    float unused;
-    if (cc.vertexUV && normalMap && in.texNormal >= 0) {
-        const f3 tangent = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexTangent)) * normalSign;
-        const f3 binormal = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexBinormal)) * normalSign;
-        const float s = mat.uvDetailScale;
-        const f4 tex = tex_sample_lod(tex_view(P.textures + in.texNormal), vd.vertexUV.x * s, vd.vertexUV.y * s, lod, in.filter, in.hAddr, in.vAddr, unused);
-        const f3 nc = mk3(tex.x * 2.0f - 1.0f, tex.y * 2.0f - 1.0f, tex.z * 2.0f - 1.0f);
-        vertexNormal = normalize3((vertexNormal * nc.z + tangent * nc.x) + binormal * nc.y);
-    }
-    r.normal = vertexNormal;
-    r.specular = mk3s(1.0f);                                                                // H9
-    if (cc.vertexUV && specularMap && in.texSpecular >= 0) {
-        const float s = mat.uvDetailScale;
-        const f4 tex = tex_sample_lod(tex_view(P.textures + in.texSpecular), vd.vertexUV.x * s, vd.vertexUV.y * s, lod, in.filter, in.hAddr, in.vAddr, unused);
-        r.specular = xyz(tex);
-    }
-    r.selfLight = ld_v3(mat.selfLight);
-    r.ignoreNormalFactor = mat.ignoreNormalFactor; r.shadowRayBias = mat.shadowRayBias; r.specularExponent = mat.specularExponent;
-    r.mask = mat.lightGroupMaskBits;
-}
 
 template <bool CACHED>
 __global__ __launch_bounds__(RT_BLOCK) void hit_light_kernel(FrameParams Pv, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, RT64_RAY_LIGHTING *lighting, uint64_t count) {
@@ -87,13 +50,7 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_light_kernel(FrameParams Pv, con
         TraceCounts cnt; cnt.nodes = 0; cnt.tris = 0;
         if (real) {
             const f3 position = pt.position, normal = pt.normal, specular = pt.specular;
-            {                                                                               // P7: passes.hip:299-304
-                const float eyeLambert = fmaxf(dot3(normal, -rayDirection), 0.0f);
-                const f3 eyeReflected = reflect3(rayDirection, normal);
-                const float eyeSpec = s_pow(fmaxf(saturatef(dot3(eyeReflected, -rayDirection)), 0.0f), pt.specularExponent);
-                const f3 eyeD = mk3(P.eyeLightDiffuseColor[0], P.eyeLightDiffuseColor[1], P.eyeLightDiffuseColor[2]), eyeS = mk3(P.eyeLightSpecularColor[0], P.eyeLightSpecularColor[1], P.eyeLightSpecularColor[2]);
-                emitted = pt.selfLight + (eyeD * eyeLambert + eyeS * (specular * eyeSpec));
-            }
+            emitted = eye_light(P, pt, rayDirection);                                       // P7
             if (pt.mask == 0u) pt.flags |= RT64_LIGHTING_UNLIT;                             // P4: shade.h:645
             else {
                 uint32_t l = 0;
@@ -103,30 +60,9 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_light_kernel(FrameParams Pv, con
                     if (!(light_intensity_simple(L, position, normal, pt.ignoreNormalFactor) > RT_EPSILON)) continue;
                     admitted++;
                     // P5: shade.h:596-632 at lightPointRadius 0, maxSamples 1 (samplePosition = lp, rs = 1)
-                    const f3 lp = ld_v3(L.position);
-                    const float sampleDistance = len3_exact(position - lp);
-                    const f3 sampleDirection = normalize3_exact(lp - position);
-                    const float sampleIntensityFactor = s_pow(fmaxf(1.0f - s_div(sampleDistance, L.attenuationRadius), 0.0f), L.attenuationExponent);
-                    const f3 reflectedLight = reflect3(-sampleDirection, normal);
-                    const float NdotL = fmaxf(dot3(normal, sampleDirection), 0.0f);
-                    const float sampleLambert = lerpf(NdotL, 1.0f, pt.ignoreNormalFactor) * sampleIntensityFactor;
-                    const float sp = s_pow(fmaxf(saturatef(dot3(reflectedLight, -rayDirection) * sampleIntensityFactor), 0.0f), pt.specularExponent);
-                    const f3 term = ld_v3(L.diffuseColor) * sampleLambert + ld_v3(L.specularColor) * (specular * sp);
-                    // P6: shade.h:623's ray, walked as visibility_query_kernel walks (K5-K7)
-                    const float o[3] = { position.x, position.y, position.z }, d[3] = { sampleDirection.x, sampleDirection.y, sampleDirection.z };
-                    const float tmin = RT_RAY_MIN_DISTANCE + pt.shadowRayBias, tmax = sampleDistance - L.shadowOffset;
-                    float visibility = 1.0f;
-                    if (query_ray_valid(o, d, tmin, tmax)) {
-                        trace_ray<CACHED>(P, o, d, tmin, tmax, false, stk,
-                                          [&](float, float hu, float hv, uint32_t hitInstance, uint32_t hitPrim, float &, uint32_t instFlags, float) -> bool {
-                                              if (instFlags & GPU_INST_SHADOW_OPAQUE) { visibility = 0.0f; return true; }      // K6
-                                              float sa = 0.0f;
-                                              waterfall(hitInstance, [&](uint32_t k) { sa = shadow_alpha_before_noise(P, inst_view(P, k), hitPrim, hu, hv); });
-                                              if (sa < 0.0f) return false;
-                                              visibility = fmaxf(visibility - sa, 0.0f);
-                                              return !(visibility > 0.0f);
-                                          }, cnt);
-                    }
+                    const LightSample ls = light_sample(position, ld_v3(L.position), normal, rayDirection, L, pt.ignoreNormalFactor, pt.specularExponent);
+                    const f3 term = ld_v3(L.diffuseColor) * ls.lambert + ld_v3(L.specularColor) * (specular * ls.sp);
+                    const float visibility = sample_visibility<CACHED>(P, pt, ls, L, stk, cnt);          // P6
                     if (!(visibility > 0.0f)) blocked++;
                     unshadowed = unshadowed + term;
                     direct = direct + term * visibility;
@@ -148,11 +84,7 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_light_kernel(FrameParams Pv, con
 }  // namespace
 
 hipError_t launch_hit_light(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *lighting, uint64_t count, hipStream_t s) {
-    if (!count) return hipSuccess;
-    const dim3 grid = query_grid(count), block(RT_BLOCK);
-    const RT64_RAY *r = static_cast<const RT64_RAY *>(rays); const RT64_RAY_HIT *h = static_cast<const RT64_RAY_HIT *>(hits);
-    const float *l = static_cast<const float *>(lods); RT64_RAY_LIGHTING *o = static_cast<RT64_RAY_LIGHTING *>(lighting);
-    if (P.cacheWords) hipLaunchKernelGGL((hit_light_kernel<true>), grid, block, (size_t)P.cacheWords * 16, s, P, r, h, l, o, count);
-    else hipLaunchKernelGGL((hit_light_kernel<false>), grid, block, 0, s, P, r, h, l, o, count);
-    return hipGetLastError();
+    decltype(&hit_light_kernel<false>) kernels[2] = { hit_light_kernel<false>, hit_light_kernel<true> };
+    return launch_cached(kernels, P, count, 0, s, static_cast<const RT64_RAY *>(rays), static_cast<const RT64_RAY_HIT *>(hits), static_cast<const float *>(lods),
+                         static_cast<RT64_RAY_LIGHTING *>(lighting), count);
 }

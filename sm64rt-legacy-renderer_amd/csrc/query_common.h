@@ -1,8 +1,9 @@
-// query_common.h -- the scaffold the ray-query kernels share (query.hip, alpha_query.hip, surface.hip, material.hip).
+// query_common.h -- the scaffold every ray-query kernel shares (launch shape and launch lines, record loads and stores, the walk's prologue).  What the
+// kernels that light a point share beyond it -- the shaded point, the light sample, the shadow walk -- is query_shading.h.
 //
 // Every query kernel runs one record per lane, RT_BLOCK threads per workgroup, at most RT_GRID_BLOCKS workgroups that stride over the records in the order given
 // (no sorting: a caller that wants coherent waves hands coherent rays in neighbouring slots), with 16-byte loads and stores.
-//   A walk kernel (rays -> hits) is its launch line (launch_walk), fill_cache + lane_stack, load_ray + query_ray_valid, trace_ray of trace.h with its own hit handler,
+//   A walk kernel (rays -> hits) is its launch line (launch_walk, or launch_cached for a kernel with one template switch), fill_cache + lane_stack, load_ray + query_ray_valid, trace_ray of trace.h with its own hit handler,
 //   and its record store (the macro STORE_QUERY_HIT for an RT64_RAY_HIT).  The walk runs from the LDS scene cache when the frame's table slot has a cache image,
 //   otherwise the one-step-per-trip HBM walk with its LDS stack and the query's spill slab.
 //   A resolve kernel (rays + hits -> records) is load_ray + load_hit, its own miss record and per-hit function, and its own record pack.  No LDS, no stack.  The
@@ -31,6 +32,12 @@ template <class K, class... A> hipError_t launch_walk(K (&kernels)[2][2], const 
     const uint32_t cull = (flags & RT64_RAY_FLAG_CULL_BACK_FACING) ? 1u : 0u;
     const bool first = (flags & RT64_RAY_FLAG_ACCEPT_FIRST_HIT) != 0, cached = P.cacheWords != 0;
     hipLaunchKernelGGL(kernels[first][cached], query_grid(count), dim3(RT_BLOCK), (size_t)P.cacheWords * 16, s, P, args..., count, cull);
+    return hipGetLastError();
+}
+// Launches the CACHED instantiation the frame's cache image selects: kernels[cached]; `extraLds` are the kernel's own dynamic LDS bytes behind the cache image, `args` its arguments after P.
+template <class K, class... A> hipError_t launch_cached(K (&kernels)[2], const FrameParams &P, uint64_t count, size_t extraLds, hipStream_t s, A... args) {
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(kernels[P.cacheWords != 0], query_grid(count), dim3(RT_BLOCK), (size_t)P.cacheWords * 16 + extraLds, s, P, args...);
     return hipGetLastError();
 }
 

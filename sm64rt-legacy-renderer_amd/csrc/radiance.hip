@@ -18,14 +18,14 @@
 //                             wave whose lanes agree on it, per-lane inst_view otherwise.  The frame constants are read per loop trip (kernel_params_here, as the
 //                             frame's tile loops do): carried across the trips, the scalar loads of the sky's, the fog's and the lights' parameters left a dead
 //                             spill slot in the frame (profiles/radiance_kernel_identity.txt); the Makefile compiles this file without the SLP vectorizer.
-// What is restated, and from where.  layer_colour is the colour half of material_of_hit (material.hip) up to H6, then the frame's UNORM8 store (shade.h, rec.color):
-// the same calls in the same order, so its alpha is surface_alpha_at_lod's bit for bit (alpha.h says why) and `transmittance` is layer_weight_kernel's.  point_of_hit
-// and the light loop with its shadow handler are hit_light_kernel's (lighting.hip), statement for statement, without the eye light, the `unshadowed` sum and the
-// counters.  They are restated, not lifted into a header both files include: lighting.hip stays byte for byte what it was, which keeps hit_light_kernel's machine
-// code out of question (footprint.hip's head comment has what such a lift did to 41 frame kernels).  tests/test_gpu_radiance_query.py holds the restatements to
-// RT64_ShadeViewRayHits and RT64_LightViewRayHits through the records (the composition identity).
-#include "query_common.h"
-#include "alpha.h"
+// What is restated.  layer_colour is the colour half of material_of_hit (material.hip) up to H6, then the frame's UNORM8 store (shade.h, rec.color): the same
+// calls in the same order, so its alpha is surface_alpha_at_lod's bit for bit (alpha.h says why) and `transmittance` is layer_weight_kernel's.  One function for
+// both was built and not kept: hit_material_kernel measured 2-3 % slower on shuffled rays with it (profiles/query_shading_kernel_identity.txt).
+// What is shared.  The shaded point, the light sample and the shadow walk are query_shading.h's (point_of_hit, light_sample, sample_visibility), the copy
+// hit_light_kernel calls; the admission loop around them is that kernel's without the eye light, the `unshadowed` sum and the counters, and the point's `flags`
+// are not read here (the compiler drops them).  tests/test_gpu_radiance_query.py holds the records to RT64_ShadeViewRayHits and RT64_LightViewRayHits (the
+// composition identity).
+#include "query_shading.h"
 #include "../../include/rt64_radiance.h"
 
 namespace {
@@ -124,42 +124,6 @@ DEV void layer_step(PRef P, const InstView &in, const QueryHit &h, uint32_t l, f
     if (s.rem <= RT_EPSILON) s.flags |= RT64_RADIANCE_COVERED;
 }
 
-struct LightPoint { f3 position, normal, specular, selfLight; float ignoreNormalFactor, shadowRayBias, specularExponent; uint32_t mask; };
-
-// lighting.hip's point_of_hit (P2 and the material fields of P4-P6), without its flags
-DEV void point_of_hit(PRef P, const InstView &in, uint32_t prim, float u, float v, f3 rayDirW, float lod, LightPoint &r) {
-    const GpuCombiner &cc = in.cc;
-    const RT64_MATERIAL &mat = in.material;
-    const bool normalMap = (in.flags & GPU_INST_NORMAL_MAP) != 0, specularMap = (in.flags & GPU_INST_SPECULAR_MAP) != 0;
-    const float b[3] = { 1.0f - u - v, u, v };
-    VertexData vd;
-    get_vertex_data(in, prim, b, cc.vertexUV && normalMap, vd);
-    r.position = mul_point(in.objectToWorld.m, vd.vertexPosition);                          // A4
-    f3 vertexNormal = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexNormal));    // H8
-    const bool back = dot3(vd.triangleNormal, rayDirW) > 0.0f;
-    const float normalSign = back ? -1.0f : 1.0f;
-    vertexNormal = vertexNormal * normalSign;
-    float unused;
-    if (cc.vertexUV && normalMap && in.texNormal >= 0) {
-        const f3 tangent = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexTangent)) * normalSign;
-        const f3 binormal = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexBinormal)) * normalSign;
-        const float s = mat.uvDetailScale;
-        const f4 tex = tex_sample_lod(tex_view(P.textures + in.texNormal), vd.vertexUV.x * s, vd.vertexUV.y * s, lod, in.filter, in.hAddr, in.vAddr, unused);
-        const f3 nc = mk3(tex.x * 2.0f - 1.0f, tex.y * 2.0f - 1.0f, tex.z * 2.0f - 1.0f);
-        vertexNormal = normalize3((vertexNormal * nc.z + tangent * nc.x) + binormal * nc.y);
-    }
-    r.normal = vertexNormal;
-    r.specular = mk3s(1.0f);                                                                // H9
-    if (cc.vertexUV && specularMap && in.texSpecular >= 0) {
-        const float s = mat.uvDetailScale;
-        const f4 tex = tex_sample_lod(tex_view(P.textures + in.texSpecular), vd.vertexUV.x * s, vd.vertexUV.y * s, lod, in.filter, in.hAddr, in.vAddr, unused);
-        r.specular = xyz(tex);
-    }
-    r.selfLight = ld_v3(mat.selfLight);
-    r.ignoreNormalFactor = mat.ignoreNormalFactor; r.shadowRayBias = mat.shadowRayBias; r.specularExponent = mat.specularExponent;
-    r.mask = mat.lightGroupMaskBits;
-}
-
 // SHADOWS = false (RT64_RADIANCE_FLAG_UNSHADOWED): nothing is walked, so the kernel has no stack and no scene cache -- a resolve kernel like layer_weight_kernel
 template <bool SHADOWS, bool CACHED>
 __global__ __launch_bounds__(RT_BLOCK) void ray_radiance_kernel(FrameParams Pv, const RT64_RAY *rays, const RT64_RAY_HIT *hits, const float *lods, RT64_RAY_RADIANCE *radiance,
@@ -222,32 +186,9 @@ __global__ __launch_bounds__(RT_BLOCK) void ray_radiance_kernel(FrameParams Pv, 
                     if (!(light_intensity_simple(L, position, normal, pt.ignoreNormalFactor) > RT_EPSILON)) continue;
                     admitted++;
                     // P5
-                    const f3 lp = ld_v3(L.position);
-                    const float sampleDistance = len3_exact(position - lp);
-                    const f3 sampleDirection = normalize3_exact(lp - position);
-                    const float sampleIntensityFactor = s_pow(fmaxf(1.0f - s_div(sampleDistance, L.attenuationRadius), 0.0f), L.attenuationExponent);
-                    const f3 reflectedLight = reflect3(-sampleDirection, normal);
-                    const float NdotL = fmaxf(dot3(normal, sampleDirection), 0.0f);
-                    const float sampleLambert = lerpf(NdotL, 1.0f, pt.ignoreNormalFactor) * sampleIntensityFactor;
-                    const float sp = s_pow(fmaxf(saturatef(dot3(reflectedLight, -rayDirection) * sampleIntensityFactor), 0.0f), pt.specularExponent);
-                    const f3 term = ld_v3(L.diffuseColor) * sampleLambert + ld_v3(L.specularColor) * (specular * sp);
-                    // P6
-                    float visibility = 1.0f;
-                    if (SHADOWS) {
-                        const float o[3] = { position.x, position.y, position.z }, d[3] = { sampleDirection.x, sampleDirection.y, sampleDirection.z };
-                        const float tmin = RT_RAY_MIN_DISTANCE + pt.shadowRayBias, tmax = sampleDistance - L.shadowOffset;
-                        if (query_ray_valid(o, d, tmin, tmax)) {
-                            trace_ray<CACHED>(P, o, d, tmin, tmax, false, stk,
-                                              [&](float, float hu, float hv, uint32_t hitInstance, uint32_t hitPrim, float &, uint32_t instFlags, float) -> bool {
-                                                  if (instFlags & GPU_INST_SHADOW_OPAQUE) { visibility = 0.0f; return true; }      // K6
-                                                  float sa = 0.0f;
-                                                  waterfall(hitInstance, [&](uint32_t w) { sa = shadow_alpha_before_noise(P, inst_view(P, w), hitPrim, hu, hv); });
-                                                  if (sa < 0.0f) return false;
-                                                  visibility = fmaxf(visibility - sa, 0.0f);
-                                                  return !(visibility > 0.0f);
-                                              }, cnt);
-                        }
-                    }
+                    const LightSample ls = light_sample(position, ld_v3(L.position), normal, rayDirection, L, pt.ignoreNormalFactor, pt.specularExponent);
+                    const f3 term = ld_v3(L.diffuseColor) * ls.lambert + ld_v3(L.specularColor) * (specular * ls.sp);
+                    const float visibility = SHADOWS ? sample_visibility<CACHED>(P, pt, ls, L, stk, cnt) : 1.0f;          // P6
                     direct = direct + term * visibility;
                 }
                 if (k < P.lightCount) flags |= RT64_RADIANCE_TRUNCATED;
@@ -288,12 +229,13 @@ hipError_t launch_pixel_sky(const FrameParams &P, const void *pixels, uint64_t f
 
 hipError_t launch_ray_radiance(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *radiance, uint64_t count, uint32_t maxLayers, uint32_t flags, hipStream_t s) {
     if (!count) return hipSuccess;
-    const dim3 grid = query_grid(count), block(RT_BLOCK);
     const RT64_RAY *r = static_cast<const RT64_RAY *>(rays); const RT64_RAY_HIT *h = static_cast<const RT64_RAY_HIT *>(hits);
     const float *l = static_cast<const float *>(lods); RT64_RAY_RADIANCE *o = static_cast<RT64_RAY_RADIANCE *>(radiance);
     const uint32_t fogFromCamera = (flags & RT64_RADIANCE_FLAG_FOG_FROM_CAMERA) ? 1u : 0u;
-    if (flags & RT64_RADIANCE_FLAG_UNSHADOWED) hipLaunchKernelGGL((ray_radiance_kernel<false, false>), grid, block, 0, s, P, r, h, l, o, count, maxLayers, fogFromCamera);
-    else if (P.cacheWords) hipLaunchKernelGGL((ray_radiance_kernel<true, true>), grid, block, (size_t)P.cacheWords * 16, s, P, r, h, l, o, count, maxLayers, fogFromCamera);
-    else hipLaunchKernelGGL((ray_radiance_kernel<true, false>), grid, block, 0, s, P, r, h, l, o, count, maxLayers, fogFromCamera);
-    return hipGetLastError();
+    if (flags & RT64_RADIANCE_FLAG_UNSHADOWED) {
+        hipLaunchKernelGGL((ray_radiance_kernel<false, false>), query_grid(count), dim3(RT_BLOCK), 0, s, P, r, h, l, o, count, maxLayers, fogFromCamera);
+        return hipGetLastError();
+    }
+    decltype(&ray_radiance_kernel<true, false>) kernels[2] = { ray_radiance_kernel<true, false>, ray_radiance_kernel<true, true> };
+    return launch_cached(kernels, P, count, 0, s, r, h, l, o, count, maxLayers, fogFromCamera);
 }

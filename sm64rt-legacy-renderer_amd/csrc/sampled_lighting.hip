@@ -11,53 +11,14 @@
 //   as pass_common.h's light_slots sizes them for the frame kernels.  A float access is one ds instruction whose lanes sit on 64 consecutive words whatever slot each
 //   lane asks for; the bytes of a slot share 16 words, four lanes a word.
 //   The drawn light differs per lane: it is fetched by shade.h's `waterfall`, one scalar pass per distinct light of the wave, as compute_light does (shade.h:595).
-//   The shadow handler is visibility_query_kernel's / hit_light_kernel's, statement for statement (alpha_query.hip; its head comment has the open defect of the
-//   `waterfall` form), with J8's factor applied to the alpha of a caster whose combiner has the noise option (shade.h:538-541).
-// The arithmetic restates shade.h with the key (x, y, frame) for (px, py, P.frameCount): compute_lights_random (:636-672) and compute_light (:592-633), the shadow term
-// kept apart from the light's term so that `unshadowed` and `direct` come from the same numbers; light_intensity_simple, blue_noise, init_rand and next_rand are called.
-// point_of_hit is lighting.hip's (:21-55), copied: the frame kernels compile neither.
-#include "query_common.h"
-#include "alpha.h"
+//   The shaded point, the eye light, the light sample and the shadow walk are query_shading.h's, the copy hit_light_kernel calls; the walk is its NOISE form, J8's
+//   factor applied to the alpha of a caster whose combiner has the noise option (shade.h:538-541; shadow_visibility has the open defect of its `waterfall` handler).
+// The arithmetic restates shade.h with the key (x, y, frame) for (px, py, P.frameCount): compute_lights_random (:636-672) and the disc of compute_light (:594-608), the
+// shadow term kept apart from the light's term so that `unshadowed` and `direct` come from the same numbers; light_intensity_simple, blue_noise, init_rand and
+// next_rand are called.
+#include "query_shading.h"
 
 namespace {
-
-struct LightPoint { f3 position, normal, specular, selfLight; float ignoreNormalFactor, shadowRayBias, specularExponent; uint32_t mask, flags; };
-
-// J2 and the material fields of J5-J9 for one real hit of instance `in`: lighting.hip:21-55
-DEV void point_of_hit(PRef P, const InstView &in, uint32_t prim, float u, float v, f3 rayDirW, float lod, LightPoint &r) {
-    const GpuCombiner &cc = in.cc;
-    const RT64_MATERIAL &mat = in.material;
-    const bool normalMap = (in.flags & GPU_INST_NORMAL_MAP) != 0, specularMap = (in.flags & GPU_INST_SPECULAR_MAP) != 0;
-    const float b[3] = { 1.0f - u - v, u, v };
-    VertexData vd;
-    get_vertex_data(in, prim, b, cc.vertexUV && normalMap, vd);
-    r.flags = RT64_SAMPLED_LIGHTING_VALID;
-    r.position = mul_point(in.objectToWorld.m, vd.vertexPosition);                          // A4
-    f3 vertexNormal = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexNormal));    // H8
-    const bool back = dot3(vd.triangleNormal, rayDirW) > 0.0f;
-    const float normalSign = back ? -1.0f : 1.0f;
-    if (back) r.flags |= RT64_SAMPLED_LIGHTING_BACK_FACE;
-    vertexNormal = vertexNormal * normalSign;
-    float unused;
-    if (cc.vertexUV && normalMap && in.texNormal >= 0) {
-        const f3 tangent = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexTangent)) * normalSign;
-        const f3 binormal = normalize3(mul_vector(in.objectToWorldNormal.m, vd.vertexBinormal)) * normalSign;
-        const float s = mat.uvDetailScale;
-        const f4 tex = tex_sample_lod(tex_view(P.textures + in.texNormal), vd.vertexUV.x * s, vd.vertexUV.y * s, lod, in.filter, in.hAddr, in.vAddr, unused);
-        const f3 nc = mk3(tex.x * 2.0f - 1.0f, tex.y * 2.0f - 1.0f, tex.z * 2.0f - 1.0f);
-        vertexNormal = normalize3((vertexNormal * nc.z + tangent * nc.x) + binormal * nc.y);
-    }
-    r.normal = vertexNormal;
-    r.specular = mk3s(1.0f);                                                                // H9
-    if (cc.vertexUV && specularMap && in.texSpecular >= 0) {
-        const float s = mat.uvDetailScale;
-        const f4 tex = tex_sample_lod(tex_view(P.textures + in.texSpecular), vd.vertexUV.x * s, vd.vertexUV.y * s, lod, in.filter, in.hAddr, in.vAddr, unused);
-        r.specular = xyz(tex);
-    }
-    r.selfLight = ld_v3(mat.selfLight);
-    r.ignoreNormalFactor = mat.ignoreNormalFactor; r.shadowRayBias = mat.shadowRayBias; r.specularExponent = mat.specularExponent;
-    r.mask = mat.lightGroupMaskBits;
-}
 
 // slots of a lane's candidate columns: pass_common.h's light_slots
 DEV uint32_t column_slots(PRef P) { return (P.lightCount < RT64_MAX_LIGHTS ? P.lightCount : (uint32_t)RT64_MAX_LIGHTS) + 1u; }
@@ -106,13 +67,7 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_sampled_light_kernel(FrameParams
         TraceCounts cnt; cnt.nodes = 0; cnt.tris = 0;
         if (real) {
             const f3 position = pt.position, normal = pt.normal, specular = pt.specular;
-            {                                                                               // J9: passes.hip:299-304
-                const float eyeLambert = fmaxf(dot3(normal, -rayDirection), 0.0f);
-                const f3 eyeReflected = reflect3(rayDirection, normal);
-                const float eyeSpec = s_pow(fmaxf(saturatef(dot3(eyeReflected, -rayDirection)), 0.0f), pt.specularExponent);
-                const f3 eyeD = mk3(P.eyeLightDiffuseColor[0], P.eyeLightDiffuseColor[1], P.eyeLightDiffuseColor[2]), eyeS = mk3(P.eyeLightSpecularColor[0], P.eyeLightSpecularColor[1], P.eyeLightSpecularColor[2]);
-                emitted = pt.selfLight + (eyeD * eyeLambert + eyeS * (specular * eyeSpec));
-            }
+            emitted = eye_light(P, pt, rayDirection);                                       // J9
             if (pt.mask == 0u) pt.flags |= RT64_SAMPLED_LIGHTING_UNLIT;                     // J5: shade.h:645
             else {
                 float total = 0.0f;
@@ -164,34 +119,10 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_sampled_light_kernel(FrameParams
                             scx = scx * rlen * sat; scy = scy * rlen * sat;
                             samplePosition = (lp + (perpX * scx) * lightPointRadius) + (perpY * scy) * lightPointRadius;
                         }
-                        const float sampleDistance = len3_exact(position - samplePosition);
-                        const f3 sampleDirection = normalize3_exact(samplePosition - position);
-                        const float sampleIntensityFactor = s_pow(fmaxf(1.0f - s_div(sampleDistance, L.attenuationRadius), 0.0f), L.attenuationExponent);
-                        const f3 reflectedLight = reflect3(-sampleDirection, normal);
-                        const float NdotL = fmaxf(dot3(normal, sampleDirection), 0.0f);
-                        const float sampleLambert = lerpf(NdotL, 1.0f, pt.ignoreNormalFactor) * sampleIntensityFactor;
-                        // J8: shade.h:623's ray, walked as visibility_query_kernel walks (K5-K7), the caster's noise included
-                        const float o[3] = { position.x, position.y, position.z }, d[3] = { sampleDirection.x, sampleDirection.y, sampleDirection.z };
-                        const float tmin = RT_RAY_MIN_DISTANCE + pt.shadowRayBias, tmax = sampleDistance - L.shadowOffset;
-                        float visibility = 1.0f;
-                        if (query_ray_valid(o, d, tmin, tmax)) {
-                            trace_ray<CACHED>(P, o, d, tmin, tmax, false, stk,
-                                              [&](float, float hu, float hv, uint32_t hitInstance, uint32_t hitPrim, float &, uint32_t instFlags, float) -> bool {
-                                                  if (instFlags & GPU_INST_SHADOW_OPAQUE) { visibility = 0.0f; return true; }      // K6
-                                                  float sa = 0.0f;
-                                                  waterfall(hitInstance, [&](uint32_t k) {
-                                                      const InstView in = inst_view(P, k);
-                                                      sa = shadow_alpha_before_noise(P, in, hitPrim, hu, hv);
-                                                      if (!(sa < 0.0f) && in.cc.optNoise) sa *= noiseFactor;
-                                                  });
-                                                  if (sa < 0.0f) return false;
-                                                  visibility = fmaxf(visibility - sa, 0.0f);
-                                                  return !(visibility > 0.0f);
-                                              }, cnt);
-                        }
-                        const float sp = s_pow(fmaxf(saturatef(dot3(reflectedLight, -rayDirection) * sampleIntensityFactor), 0.0f), pt.specularExponent);
-                        lLambert += sampleLambert * rs;
-                        lSpec = lSpec + (specular * sp) * rs;
+                        const LightSample ls = light_sample(position, samplePosition, normal, rayDirection, L, pt.ignoreNormalFactor, pt.specularExponent);
+                        const float visibility = sample_visibility<CACHED, true>(P, pt, ls, L, stk, cnt, noiseFactor);          // J8: the caster's noise included
+                        lLambert += ls.lambert * rs;
+                        lSpec = lSpec + (specular * ls.sp) * rs;
                         lShadow += visibility * rs;
                     }
                     const f3 term = ld_v3(L.diffuseColor) * lLambert + ld_v3(L.specularColor) * lSpec;
@@ -215,14 +146,9 @@ __global__ __launch_bounds__(RT_BLOCK) void hit_sampled_light_kernel(FrameParams
 
 hipError_t launch_hit_sampled_light(const FrameParams &P, const void *rays, const void *hits, const void *lods, const void *keys, uint64_t first, uint32_t maxLights, uint32_t diSamples,
                                     void *records, uint64_t count, hipStream_t s) {
-    if (!count) return hipSuccess;
-    const dim3 grid = query_grid(count), block(RT_BLOCK);
-    const RT64_RAY *r = static_cast<const RT64_RAY *>(rays); const RT64_RAY_HIT *h = static_cast<const RT64_RAY_HIT *>(hits);
-    const float *l = static_cast<const float *>(lods); const RT64_LIGHT_SAMPLE_KEY *k = static_cast<const RT64_LIGHT_SAMPLE_KEY *>(keys);
-    RT64_RAY_SAMPLED_LIGHTING *o = static_cast<RT64_RAY_SAMPLED_LIGHTING *>(records);
+    decltype(&hit_sampled_light_kernel<false>) kernels[2] = { hit_sampled_light_kernel<false>, hit_sampled_light_kernel<true> };
     // the candidate columns behind the cache image: slots x RT_BLOCK floats, then slots x RT_BLOCK bytes
     const size_t slots = (P.lightCount < RT64_MAX_LIGHTS ? P.lightCount : (uint32_t)RT64_MAX_LIGHTS) + 1u, columns = slots * RT_BLOCK * (sizeof(float) + 1);
-    if (P.cacheWords) hipLaunchKernelGGL((hit_sampled_light_kernel<true>), grid, block, (size_t)P.cacheWords * 16 + columns, s, P, r, h, l, k, first, maxLights, diSamples, o, count);
-    else hipLaunchKernelGGL((hit_sampled_light_kernel<false>), grid, block, columns, s, P, r, h, l, k, first, maxLights, diSamples, o, count);
-    return hipGetLastError();
+    return launch_cached(kernels, P, count, columns, s, static_cast<const RT64_RAY *>(rays), static_cast<const RT64_RAY_HIT *>(hits), static_cast<const float *>(lods),
+                         static_cast<const RT64_LIGHT_SAMPLE_KEY *>(keys), first, maxLights, diSamples, static_cast<RT64_RAY_SAMPLED_LIGHTING *>(records), count);
 }

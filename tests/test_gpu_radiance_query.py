@@ -195,7 +195,7 @@ ROUNDINGS = 32
 
 @pytest.mark.parametrize("name", RC.NAMES)
 def test_the_record_is_the_composition_of_the_existing_calls(rt64_lib, sample_data, name):
-    """2.  The sentence of rt64_layers.h, tested, and the restated copies in radiance.hip held to material.hip and lighting.hip more closely than the rule's bound
+    """2.  The sentence of rt64_layers.h, tested, and radiance.hip's layer colour and light held to the records of material.hip and lighting.hip more closely than the rule's bound
     can (the independent check is test 1; this one shares the library's own colours and lights): recomputed from RT64_TraceViewRayLayers' weights, RT64_ShadeViewRayHits per layer, RT64_LightViewRayHits at litLayer and
     RT64_SkyViewRays, transmittance and layers match bit for bit, litLayer and the flags exactly, and every colour within ROUNDINGS x 2^-24 of the terms' magnitudes --
     shadowed and UNSHADOWED, fog from the origin and (fog_8) from the camera."""
