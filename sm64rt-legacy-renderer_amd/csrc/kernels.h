@@ -221,3 +221,22 @@ hipError_t launch_pixel_sky(const FrameParams &P, const void *pixels, uint64_t f
 // 16-byte aligned; lods 4; rules W3-W7); 1 <= maxLayers <= 16.  flags: RT64_RADIANCE_FLAG_*.  One shadow walk per admitted light of the lit layer unless UNSHADOWED:
 // P.traversalStack as for launch_ray_query.
 hipError_t launch_ray_radiance(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *radiance, uint64_t count, uint32_t maxLayers, uint32_t flags, hipStream_t s);
+
+// ---- indirect.hip ---------------------------------------------------------------------------------------------------
+// The links of the GI chain (include/rt64_indirect.h; rules Y1-Y12); device pointers, 16-byte aligned.  Ray i of a launch belongs to point i % points (key keys[i % points],
+// or -- keys == nullptr -- pixel first + i % points of the frame, row by row) and is sample slot slotTop - i / points of it; points < count only with count < 2^32.
+// RT64_GenerateViewPointGIRays: `count` bounce rays (Y4).  source: 16-byte words, the position word of source record r at source[r * strideWords], its normal word behind it;
+// perRay: record i belongs to ray i, otherwise to the ray's point; a record is used if its flags hold needFlags and none of refuseFlags.  giSamples >= 1.  Reads only P.
+hipError_t launch_gi_rays(const FrameParams &P, const void *source, uint32_t strideWords, bool perRay, uint32_t needFlags, uint32_t refuseFlags, const void *keys, uint64_t first,
+                          uint64_t points, uint32_t giSamples, uint32_t slotTop, bool second, void *rays, uint64_t count, hipStream_t s);
+// RT64_ComposeViewGIRays: `count` RT64_RAYs and their maxLayers * count RT64_RAY_HITs, layer-major -> RT64_GI_SAMPLEs (Y5-Y7); incoming: 3 floats per ray at
+// incoming[i * incomingStride] (4-byte aligned), or nullptr.  light = false: the resolve alone (position, normal, instance, flags; radiance 0), no walk.  Otherwise one shadow
+// walk per disc sample: P.traversalStack as for launch_ray_query.
+hipError_t launch_gi_shade(const FrameParams &P, const void *rays, const void *hits, uint32_t maxLayers, const void *keys, uint64_t first, uint64_t points, const void *incoming,
+                           uint32_t incomingStride, uint32_t diSamples, bool light, void *samples, uint64_t count, hipStream_t s);
+// Y10: `count` RT64_RAYs, their RT64_RAY_HITs and (lods != nullptr) their lods -> RT64_GI_POINTs.  Reads neither P.traversalStack nor the LDS scene cache.
+hipError_t launch_gi_points(const FrameParams &P, const void *rays, const void *hits, const void *lods, void *points, uint64_t count, hipStream_t s);
+// Y8: `count` RT64_GI_POINTs and giSamples * count RT64_GI_SAMPLEs, sample-major (secondSamples: the second bounces', or nullptr; firstWalks / secondWalks: the
+// RT64_RAY_LAYERS of the rays' walks, for their counters, or nullptr) -> RT64_POINT_INDIRECTs.
+hipError_t launch_gi_accumulate(const FrameParams &P, const void *points, const void *firstSamples, const void *secondSamples, const void *firstWalks, const void *secondWalks,
+                                uint32_t giSamples, void *records, uint64_t count, hipStream_t s);

@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "device_math.h"
 #include "query_staging.h"
+#include "../../include/rt64_indirect.h"
 
 #define RT64_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -229,6 +230,7 @@ struct Device {
     DevArray<uint8_t> queryRays, queryHits, queryLods, queryKeys, queryRecords, queryPixels, queryDiffs, queryFootprints;      // queryHits: a walk's hits or visibilities; queryRecords: surfaces, materials or lighting
     DevArray<uint8_t> queryBounces, queryReflected, queryRefracted;
     DevArray<uint8_t> queryLayerSlab, queryLayers, queryWeights, queryCoverage;        // layers.hip: the payload slab of the lists being built (it takes turns like querySlab), and the staged outputs
+    DevArray<uint8_t> giPoints, giIncoming, giRays[2], giHits[2], giWalks[2], giSamples[2];      // indirect.hip: the staged points and incoming light, and the chain's scratch per bounce (rays, layer lists, RT64_RAY_LAYERS, samples); it takes turns like querySlab
     void awaitQueries();          // host-waits for every query or resolve still enqueued on a caller stream (before a BLAS, vertex or index array it may read is rewritten or freed)
     void *gatherTarget = nullptr; size_t gatherTargetBytes = 0;          // RT64_SetDeviceGatherTarget
     hipEvent_t frameWait = nullptr;       // set by the gather: the next frame's stream waits for this event before its first launch (the slot that frame writes is free then); applied by Device::draw once it knows the stream
@@ -2567,6 +2569,147 @@ static void run_view_radiance(const char *fn, View *v, const void *rays, const v
     query_finish(fn, v, c);
 }
 
+// The calls of include/rt64_indirect.h (indirect.hip; rules Y1-Y12), beside run_view_radiance.  INDIRECT_RAYS: points (+ keys) -> the bounce rays of one sample slot.
+// INDIRECT_SHADE: rays + maxLayers * count layer records (+ keys, + incoming) -> samples.  INDIRECT_CHAIN: points (+ keys) -> records (+ giSamples * count samples), the whole
+// chain per chunk.  INDIRECT_CHAIN with INDIRECT_WALK in front, host arrays only: rays (+ lods, + keys) -> RT64_TraceViewRaysAlpha's hits (`hits` an optional output) -> their
+// points -> the chain (Y10); `points` then holds the rays.
+enum : int { INDIRECT_RAYS = 1, INDIRECT_SHADE = 2, INDIRECT_CHAIN = 4, INDIRECT_WALK = 8 };
+struct GiSampling { uint32_t giSamples, giBounces, diSamples; };
+// Y11: the points of a chunk of the chain: giSamples * 16 hit records per point, at most 2^20 of them (32 MB) per bounce
+static size_t gi_chunk_points(uint32_t giSamples) { return std::max<size_t>(((size_t)1 << 20) / ((size_t)RT64_RAY_LAYERS_MAX * std::max(giSamples, 1u)), 1); }
+// The chain's scratch for chunks of at most n points, reserved before any device pointer is taken from it
+static void gi_reserve(Device *dev, const GiSampling &g, size_t n) {
+    const size_t rays = (size_t)g.giSamples * n;
+    for (uint32_t b = 0; b < (g.giSamples ? g.giBounces : 0u); b++) {
+        dev->giRays[b].reserve(rays * sizeof(RT64_RAY)); dev->giHits[b].reserve(rays * RT64_RAY_LAYERS_MAX * sizeof(RT64_RAY_HIT));
+        dev->giWalks[b].reserve(rays * sizeof(RT64_RAY_LAYERS)); dev->giSamples[b].reserve(rays * sizeof(RT64_GI_SAMPLE));
+    }
+    dev->queryLayerSlab.reserve(ray_layer_slab_bytes());
+}
+// One chunk of the chain on device arrays (Y8): n points, record 0 of them record `at` of the call (+ their keys, or NULL) -> n records; the first bounce's samples are left in
+// dev->giSamples[0], sample-major.  Every launch goes to the call's stream.
+static void gi_chain(Device *dev, const QueryCall &c, const GiSampling &g, const void *points, const void *keys, size_t at, void *records, size_t n) {
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    const uint32_t S = g.giSamples, L = RT64_RAY_LAYERS_MAX, cull = RT64_RAY_FLAG_CULL_BACK_FACING;
+    const size_t rays = (size_t)S * n;
+    const bool second = S > 0 && g.giBounces >= 2;
+    if (S > 0) {
+        void *r0 = dev->giRays[0].ptr, *h0 = dev->giHits[0].ptr, *w0 = dev->giWalks[0].ptr, *s0 = dev->giSamples[0].ptr;
+        HIP_CHECK(launch_gi_rays(R, points, 2, false, 0u, RT64_GI_POINT_NONE, keys, at, n, S, S, false, r0, rays, s));
+        HIP_CHECK(launch_layer_walk(P, r0, nullptr, h0, w0, dev->queryLayerSlab.ptr, rays, L, cull, s));
+        if (second) {          // the first bounce's resolve alone, the second ray from where it ended, and what that ray brings back
+            void *r1 = dev->giRays[1].ptr, *h1 = dev->giHits[1].ptr, *w1 = dev->giWalks[1].ptr, *s1 = dev->giSamples[1].ptr;
+            HIP_CHECK(launch_gi_shade(R, r0, h0, L, keys, at, n, nullptr, 0, g.diSamples, false, s0, rays, s));
+            HIP_CHECK(launch_gi_rays(R, static_cast<const uint8_t *>(s0) + offsetof(RT64_GI_SAMPLE, position), sizeof(RT64_GI_SAMPLE) / 16, true, RT64_GI_SAMPLE_SURFACE, 0u, keys, at, n, S, S, true, r1, rays, s));
+            HIP_CHECK(launch_layer_walk(P, r1, nullptr, h1, w1, dev->queryLayerSlab.ptr, rays, L, cull, s));
+            HIP_CHECK(launch_gi_shade(P, r1, h1, L, keys, at, n, nullptr, 0, g.diSamples, true, s1, rays, s));
+        }
+        HIP_CHECK(launch_gi_shade(P, r0, h0, L, keys, at, n, second ? dev->giSamples[1].ptr : nullptr, sizeof(RT64_GI_SAMPLE) / sizeof(float), g.diSamples, true, s0, rays, s));
+    }
+    HIP_CHECK(launch_gi_accumulate(R, points, dev->giSamples[0].ptr, second ? dev->giSamples[1].ptr : nullptr, dev->giWalks[0].ptr, second ? dev->giWalks[1].ptr : nullptr, S, records, n, s));
+}
+static void run_view_indirect(const char *fn, View *v, const void *points, void *hits, unsigned maxLayers, const void *lods, const void *keys, const void *incoming,
+                              const RT64_GI_SAMPLING *sampling, unsigned slot, unsigned flags, void *rays, void *samples, void *records, size_t count, void *stream, bool hostArrays, int work) {
+    auto fail = [&](const std::string &why) { throw std::runtime_error(std::string(fn) + ": " + why); };
+    const bool gen = (work & INDIRECT_RAYS) != 0, shade = (work & INDIRECT_SHADE) != 0, chain = (work & INDIRECT_CHAIN) != 0, walk = (work & INDIRECT_WALK) != 0;
+    if (!v) fail("NULL view.");
+    if (gen && (!points || !rays)) fail("NULL point or ray array.");
+    if (shade && (!rays || !hits || !samples)) fail("NULL ray, layer or sample array.");
+    if (chain && (!points || !records)) fail(walk ? "NULL ray or record array." : "NULL point or record array.");
+    if (gen && (flags & ~(unsigned)RT64_GI_RAYS_SECOND_BOUNCE)) fail("unknown flags (RT64_GI_RAYS_SECOND_BOUNCE only).");
+    if (walk && (flags & ~(unsigned)RT64_RAY_FLAG_CULL_BACK_FACING)) fail("unknown flags (an indirect-light query takes RT64_RAY_FLAG_CULL_BACK_FACING only).");      // Y10
+    if (shade && (maxLayers < 1u || maxLayers > (unsigned)RT64_RAY_LAYERS_MAX)) fail("maxLayers must be 1 to " + std::to_string(RT64_RAY_LAYERS_MAX) + ".");
+    if (sampling) {                                                                                                                                                // Y3
+        if (sampling->flags != 0u) fail("unknown sampling flags.");
+        if (sampling->giSamples < -1 || sampling->giSamples > RT64_GI_SAMPLING_MAX_SAMPLES) fail("giSamples must be 0 to " + std::to_string(RT64_GI_SAMPLING_MAX_SAMPLES) + ", or -1 for the last frame's.");
+        if (sampling->giBounces < -1 || sampling->giBounces == 0 || sampling->giBounces > RT64_GI_SAMPLING_MAX_BOUNCES) fail("giBounces must be 1 to " + std::to_string(RT64_GI_SAMPLING_MAX_BOUNCES) + ", or -1 for the last frame's.");
+        if (sampling->diSamples < -1 || sampling->diSamples > RT64_LIGHT_SAMPLING_MAX_SAMPLES) fail("diSamples must be 0 to " + std::to_string(RT64_LIGHT_SAMPLING_MAX_SAMPLES) + ", or -1 for the last frame's.");
+    }
+    if (!hostArrays) {
+        if ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(hits) | reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(samples) |
+             reinterpret_cast<uintptr_t>(records)) & 15u)
+            fail(gen ? "the point, key and ray arrays must be 16-byte aligned." : shade ? "the ray, layer, key and sample arrays must be 16-byte aligned." : "the point, key, sample and record arrays must be 16-byte aligned.");
+        if (reinterpret_cast<uintptr_t>(incoming) & 3u) fail("the incoming array must be 4-byte aligned.");
+    }
+    Device *dev = v->scene->device;
+    const View::QueryScene &q = v->query;
+    query_frame_check(q, !gen, !gen, fail);          // Y11: K9's; the rays alone read no mesh and no texture
+    if (!gen && q.skyDestroyed) fail("the sky texture of the view's last frame was destroyed since; draw a frame first.");
+    if (q.P.width <= 0 || q.P.height <= 0) fail("the view's last frame traced no instance: it kept no noise, no lights and no sky to sample.");
+    if (!keys && count > (size_t)q.P.width * (size_t)q.P.height) fail("more records than the frame has pixels (keys = NULL counts them row by row).");      // Y2
+    GiSampling g;
+    g.giSamples = sampling && sampling->giSamples >= 0 ? (uint32_t)sampling->giSamples : std::min(q.P.giSamples, (uint32_t)RT64_GI_SAMPLING_MAX_SAMPLES);
+    g.giBounces = sampling && sampling->giBounces >= 1 ? (uint32_t)sampling->giBounces : (q.P.giBounces >= 2u ? 2u : 1u);
+    g.diSamples = sampling && sampling->diSamples >= 0 ? (uint32_t)sampling->diSamples : q.P.diSamples;
+    if (gen && g.giSamples < 1u) fail("giSamples is 0: there is no bounce ray to generate.");                                      // Y3
+    if (gen && (slot < 1u || slot > g.giSamples)) fail("slot must be 1 to giSamples (" + std::to_string(g.giSamples) + ").");      // Y4
+    QueryCall c;
+    if (!query_start(fn, v, count, shade || chain, chain, hostArrays ? nullptr : stream, c)) return;
+    const FrameParams &P = c.P, &R = c.R; const hipStream_t s = c.s;
+    const uint32_t S = g.giSamples;
+    if (gen) {
+        auto launch = [&](const void *pt, const void *k, size_t at, void *r, size_t n) {
+            HIP_CHECK(launch_gi_rays(R, pt, sizeof(RT64_GI_POINT) / 16, false, 0u, RT64_GI_POINT_NONE, k, at, n, S, slot, (flags & RT64_GI_RAYS_SECOND_BOUNCE) != 0, r, n, s));
+        };
+        if (hostArrays)
+            query_stage(dev, s, {{&dev->giPoints, points, nullptr, sizeof(RT64_GI_POINT)},
+                                 {keys ? &dev->queryKeys : nullptr, keys, nullptr, sizeof(RT64_LIGHT_SAMPLE_KEY)},
+                                 {&dev->queryRays, nullptr, rays, sizeof(RT64_RAY)}},
+                        count, (size_t)1 << 18, [&](size_t at, size_t n) { launch(dev->giPoints.ptr, keys ? dev->queryKeys.ptr : nullptr, at, dev->queryRays.ptr, n); });
+        else launch(points, keys, 0, rays, count);
+    }
+    else if (shade) {
+        auto launch = [&](const void *r, const void *h, const void *k, const void *in, size_t at, void *out, size_t n) {
+            HIP_CHECK(launch_gi_shade(P, r, h, maxLayers, k, at, n, in, 3, g.diSamples, true, out, n, s));
+        };
+        if (hostArrays)
+            query_stage(dev, s, {{&dev->queryRays, rays, nullptr, sizeof(RT64_RAY)},
+                                 {&dev->queryHits, hits, nullptr, sizeof(RT64_RAY_HIT), maxLayers},
+                                 {keys ? &dev->queryKeys : nullptr, keys, nullptr, sizeof(RT64_LIGHT_SAMPLE_KEY)},
+                                 {incoming ? &dev->giIncoming : nullptr, incoming, nullptr, 3 * sizeof(float)},
+                                 {&dev->queryRecords, nullptr, samples, sizeof(RT64_GI_SAMPLE)}},
+                        count, std::max<size_t>(((size_t)1 << 18) / maxLayers, 1), [&](size_t at, size_t n) {
+                            launch(dev->queryRays.ptr, dev->queryHits.ptr, keys ? dev->queryKeys.ptr : nullptr, incoming ? dev->giIncoming.ptr : nullptr, at, dev->queryRecords.ptr, n);
+                        });
+        else launch(rays, hits, keys, incoming, 0, samples, count);
+    }
+    else {
+        const size_t chunk = std::min(count, gi_chunk_points(S));
+        gi_reserve(dev, g, chunk);
+        if (hostArrays) {
+            // Up [points, or rays | lods, | keys] as far as the call brings them, down [hits | samples | records] as far as it wants them.  The first bounce's samples come
+            // down from the chain's own scratch, as giSamples blocks of a chunk's points each.
+            dev->giPoints.reserve(chunk * sizeof(RT64_GI_POINT));
+            const bool wantSamples = samples && S > 0;
+            query_stage(dev, s, {{walk ? &dev->queryRays : &dev->giPoints, points, nullptr, walk ? sizeof(RT64_RAY) : sizeof(RT64_GI_POINT)},
+                                 {walk ? &dev->queryHits : nullptr, nullptr, hits, sizeof(RT64_RAY_HIT)},
+                                 {walk && lods ? &dev->queryLods : nullptr, lods, nullptr, sizeof(float)},
+                                 {keys ? &dev->queryKeys : nullptr, keys, nullptr, sizeof(RT64_LIGHT_SAMPLE_KEY)},
+                                 {wantSamples ? &dev->giSamples[0] : nullptr, nullptr, samples, sizeof(RT64_GI_SAMPLE), S},
+                                 {&dev->queryRecords, nullptr, records, sizeof(RT64_POINT_INDIRECT)}},
+                        count, chunk, [&](size_t at, size_t n) {
+                            if (walk) {
+                                HIP_CHECK(launch_alpha_query(P, dev->queryRays.ptr, lods ? dev->queryLods.ptr : nullptr, dev->queryHits.ptr, n, flags, s));
+                                HIP_CHECK(launch_gi_points(R, dev->queryRays.ptr, dev->queryHits.ptr, lods ? dev->queryLods.ptr : nullptr, dev->giPoints.ptr, n, s));
+                            }
+                            gi_chain(dev, c, g, dev->giPoints.ptr, keys ? dev->queryKeys.ptr : nullptr, at, dev->queryRecords.ptr, n);
+                        });
+        }
+        else {
+            for (size_t at = 0; at < count; at += chunk) {
+                const size_t n = std::min(chunk, count - at);
+                gi_chain(dev, c, g, static_cast<const uint8_t *>(points) + at * sizeof(RT64_GI_POINT), keys ? static_cast<const uint8_t *>(keys) + at * sizeof(RT64_LIGHT_SAMPLE_KEY) : nullptr, at,
+                         static_cast<uint8_t *>(records) + at * sizeof(RT64_POINT_INDIRECT), n);
+                if (samples) for (uint32_t k = 0; k < S; k++)          // the chunk's block of sample slot k into the caller's sample-major array
+                    HIP_CHECK(hipMemcpyAsync(static_cast<uint8_t *>(samples) + ((size_t)k * count + at) * sizeof(RT64_GI_SAMPLE), dev->giSamples[0].ptr + (size_t)k * n * sizeof(RT64_GI_SAMPLE),
+                                             n * sizeof(RT64_GI_SAMPLE), hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+    if (!gen && s != dev->stream) v->query.viewBuffersRead = true;          // the sky term reads `background` and `skyTiled`, as the calls of rt64_radiance.h
+    query_finish(fn, v, c);
+}
+
 }  // namespace rt64
 
 // ======================================================================================================================================
@@ -2776,6 +2919,29 @@ RT64_EXPORT int RT64_SampleViewRayLightsDevice(RT64_VIEW *view, const void *rays
 RT64_EXPORT int RT64_TraceViewRaySampledLights(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, const RT64_LIGHT_SAMPLE_KEY *keys, const RT64_LIGHT_SAMPLING *sampling,
                                                  RT64_RAY_SAMPLED_LIGHTING *records, size_t count, unsigned int flags) {
     RT64_TRY run_view_sampled_light("RT64_TraceViewRaySampledLights", reinterpret_cast<View *>(view), rays, hits, lods, keys, sampling, records, count, flags, nullptr, true, true); return 1; RT64_CATCH(0)
+}
+// include/rt64_indirect.h (rules Y1-Y12; the const casts only fit the shared signature: the calls write neither points, rays nor layer records they are given)
+RT64_EXPORT int RT64_GenerateViewPointGIRays(RT64_VIEW *view, const RT64_GI_POINT *points, const RT64_LIGHT_SAMPLE_KEY *keys, const RT64_GI_SAMPLING *sampling, unsigned int slot, unsigned int flags, RT64_RAY *rays, size_t count) {
+    RT64_TRY run_view_indirect("RT64_GenerateViewPointGIRays", reinterpret_cast<View *>(view), points, nullptr, 0, nullptr, keys, nullptr, sampling, slot, flags, rays, nullptr, nullptr, count, nullptr, true, INDIRECT_RAYS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_GenerateViewPointGIRaysDevice(RT64_VIEW *view, const void *points, const void *keys, const RT64_GI_SAMPLING *sampling, unsigned int slot, unsigned int flags, void *rays, size_t count, void *stream) {
+    RT64_TRY run_view_indirect("RT64_GenerateViewPointGIRaysDevice", reinterpret_cast<View *>(view), points, nullptr, 0, nullptr, keys, nullptr, sampling, slot, flags, rays, nullptr, nullptr, count, stream, false, INDIRECT_RAYS); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_ComposeViewGIRays(RT64_VIEW *view, const RT64_RAY *rays, const RT64_RAY_HIT *layerHits, unsigned int maxLayers, const RT64_LIGHT_SAMPLE_KEY *keys, const float *incoming, const RT64_GI_SAMPLING *sampling,
+                                         RT64_GI_SAMPLE *samples, size_t count) {
+    RT64_TRY run_view_indirect("RT64_ComposeViewGIRays", reinterpret_cast<View *>(view), nullptr, const_cast<RT64_RAY_HIT *>(layerHits), maxLayers, nullptr, keys, incoming, sampling, 0, 0, const_cast<RT64_RAY *>(rays), samples, nullptr, count, nullptr, true, INDIRECT_SHADE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_ComposeViewGIRaysDevice(RT64_VIEW *view, const void *rays, const void *layerHits, unsigned int maxLayers, const void *keys, const void *incoming, const RT64_GI_SAMPLING *sampling, void *samples, size_t count, void *stream) {
+    RT64_TRY run_view_indirect("RT64_ComposeViewGIRaysDevice", reinterpret_cast<View *>(view), nullptr, const_cast<void *>(layerHits), maxLayers, nullptr, keys, incoming, sampling, 0, 0, const_cast<void *>(rays), samples, nullptr, count, stream, false, INDIRECT_SHADE); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewPointsIndirect(RT64_VIEW *view, const RT64_GI_POINT *points, const RT64_LIGHT_SAMPLE_KEY *keys, const RT64_GI_SAMPLING *sampling, RT64_GI_SAMPLE *samples, RT64_POINT_INDIRECT *records, size_t count) {
+    RT64_TRY run_view_indirect("RT64_TraceViewPointsIndirect", reinterpret_cast<View *>(view), points, nullptr, 0, nullptr, keys, nullptr, sampling, 0, 0, nullptr, samples, records, count, nullptr, true, INDIRECT_CHAIN); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewPointsIndirectDevice(RT64_VIEW *view, const void *points, const void *keys, const RT64_GI_SAMPLING *sampling, void *samples, void *records, size_t count, void *stream) {
+    RT64_TRY run_view_indirect("RT64_TraceViewPointsIndirectDevice", reinterpret_cast<View *>(view), points, nullptr, 0, nullptr, keys, nullptr, sampling, 0, 0, nullptr, samples, records, count, stream, false, INDIRECT_CHAIN); return 1; RT64_CATCH(0)
+}
+RT64_EXPORT int RT64_TraceViewRayIndirect(RT64_VIEW *view, const RT64_RAY *rays, RT64_RAY_HIT *hits, const float *lods, const RT64_LIGHT_SAMPLE_KEY *keys, const RT64_GI_SAMPLING *sampling, RT64_POINT_INDIRECT *records, size_t count, unsigned int flags) {
+    RT64_TRY run_view_indirect("RT64_TraceViewRayIndirect", reinterpret_cast<View *>(view), rays, hits, 0, lods, keys, nullptr, sampling, 0, flags, nullptr, nullptr, records, count, nullptr, true, INDIRECT_CHAIN | INDIRECT_WALK); return 1; RT64_CATCH(0)
 }
 // include/rt64_footprint.h (rules F1-F11)
 RT64_EXPORT int RT64_GenerateViewCameraRays(RT64_VIEW *view, const unsigned int *pixels, RT64_RAY *rays, RT64_RAY_DIFFERENTIAL *diffs, size_t count) {

@@ -295,6 +295,20 @@ SAMPLED_LIGHTING_API = [
 ]
 (SAMPLED_LIGHTING_VALID, SAMPLED_LIGHTING_BAD_HIT, SAMPLED_LIGHTING_BACK_FACE, SAMPLED_LIGHTING_UNLIT, SAMPLED_LIGHTING_TRUNCATED) = 0x01, 0x02, 0x04, 0x08, 0x10
 LIGHT_SAMPLING_MAX_LIGHTS, LIGHT_SAMPLING_MAX_SAMPLES = 16, 64
+# include/rt64_indirect.h: the indirect light of a point as a frame's pixel samples it (rules Y1-Y12), a list and a loader (RT64_LoadLibraryIndirect) of its own
+INDIRECT_API = [
+    ("GenerateViewPointGIRays", "RT64_GenerateViewPointGIRays", C.c_int, [_P, _P, _P, _P, C.c_uint, C.c_uint, _P, C.c_size_t]),
+    ("GenerateViewPointGIRaysDevice", "RT64_GenerateViewPointGIRaysDevice", C.c_int, [_P, _P, _P, _P, C.c_uint, C.c_uint, _P, C.c_size_t, _P]),
+    ("ComposeViewGIRays", "RT64_ComposeViewGIRays", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, _P, _P, C.c_size_t]),
+    ("ComposeViewGIRaysDevice", "RT64_ComposeViewGIRaysDevice", C.c_int, [_P, _P, _P, C.c_uint, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewPointsIndirect", "RT64_TraceViewPointsIndirect", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t]),
+    ("TraceViewPointsIndirectDevice", "RT64_TraceViewPointsIndirectDevice", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    ("TraceViewRayIndirect", "RT64_TraceViewRayIndirect", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_uint]),
+]
+GI_POINT_NONE, GI_RAYS_SECOND_BOUNCE = 0x1, 0x1
+(GI_SAMPLE_VALID, GI_SAMPLE_BAD_HIT, GI_SAMPLE_SURFACE, GI_SAMPLE_COVERED, GI_SAMPLE_UNLIT, GI_SAMPLE_TRUNCATED) = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+INDIRECT_VALID, INDIRECT_BAD_POINT, INDIRECT_BAD_HIT = 0x1, 0x2, 0x4
+GI_SAMPLING_MAX_SAMPLES, GI_SAMPLING_MAX_BOUNCES = 64, 2
 # include/rt64_radiance.h: the colour a ray brings back and the sky behind it (rules W1-W12), a list and a loader (RT64_LoadLibraryRadiance) of its own
 RADIANCE_API = [
     ("SkyViewRays", "RT64_SkyViewRays", C.c_int, [_P, _P, _P, C.c_size_t]),
@@ -385,7 +399,26 @@ class RAY_RADIANCE(C.Structure):
                 ("transparent", C.c_float * 3), ("litLayer", C.c_int), ("light", C.c_float * 3), ("layers", C.c_uint)]
 
 
+class GI_POINT(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("flags", C.c_uint), ("normal", C.c_float * 3), ("instance", C.c_int)]
+
+
+class GI_SAMPLING(C.Structure):
+    _fields_ = [("giSamples", C.c_int), ("giBounces", C.c_int), ("diSamples", C.c_int), ("flags", C.c_uint)]
+
+
+class GI_SAMPLE(C.Structure):
+    _fields_ = [("radiance", C.c_float * 3), ("remaining", C.c_float), ("position", C.c_float * 3), ("flags", C.c_uint), ("normal", C.c_float * 3), ("instance", C.c_int),
+                ("layers", C.c_uint), ("reserved", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint)]
+
+
+class POINT_INDIRECT(C.Structure):
+    _fields_ = [("indirect", C.c_float * 3), ("samples", C.c_float), ("moments", C.c_float * 2), ("flags", C.c_uint), ("instance", C.c_int),
+                ("rays", C.c_uint), ("nodesVisited", C.c_uint), ("trianglesTested", C.c_uint), ("reserved", C.c_uint)]
+
+
 assert C.sizeof(RAY_LAYERS) == 16 and C.sizeof(RAY_COVERAGE) == 16
+assert C.sizeof(GI_POINT) == 32 and C.sizeof(GI_SAMPLING) == 16 and C.sizeof(GI_SAMPLE) == 64 and C.sizeof(POINT_INDIRECT) == 48
 assert C.sizeof(LIGHT_SAMPLE_KEY) == 16 and C.sizeof(LIGHT_SAMPLING) == 16 and C.sizeof(RAY_SAMPLED_LIGHTING) == 64
 assert C.sizeof(RAY_SKY) == 32 and C.sizeof(RAY_RADIANCE) == 64
 assert C.sizeof(RAY_VISIBILITY) == 16 and C.sizeof(RAY_LIGHTING) == 64 and C.sizeof(RAY_BOUNCE) == 32
@@ -415,7 +448,7 @@ class Library:
                 "There is no CPU fallback.")
         self.path = path
         self.handle = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + SAMPLED_LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API + RADIANCE_API:
+        for member, symbol, restype, argtypes in API + EXT_API + QUERY_API + SURFACE_API + MATERIAL_API + ALPHA_API + LIGHTING_API + SAMPLED_LIGHTING_API + FOOTPRINT_API + BOUNCE_API + LAYERS_API + RADIANCE_API + INDIRECT_API:
             fn = getattr(self.handle, symbol)      # AttributeError if an export is missing
             fn.restype = restype
             fn.argtypes = argtypes
@@ -843,3 +876,110 @@ def trace_view_ray_radiance(lib, view, rays, max_layers=RAY_LAYERS_MAX, lods=Non
     if layers:
         outs[1 if hits else 0] = _as_uint32(outs[1 if hits else 0])
     return tuple(outs)
+
+
+GI_POINT_DTYPE = [("position", "<f4", (3,)), ("flags", "<u4"), ("normal", "<f4", (3,)), ("instance", "<i4")]          # numpy dtypes of the four structs of rt64_indirect.h
+GI_SAMPLING_DTYPE = [("giSamples", "<i4"), ("giBounces", "<i4"), ("diSamples", "<i4"), ("flags", "<u4")]
+GI_SAMPLE_DTYPE = [("radiance", "<f4", (3,)), ("remaining", "<f4"), ("position", "<f4", (3,)), ("flags", "<u4"), ("normal", "<f4", (3,)), ("instance", "<i4"),
+                   ("layers", "<u4"), ("reserved", "<u4"), ("nodesVisited", "<u4"), ("trianglesTested", "<u4")]
+POINT_INDIRECT_DTYPE = [("indirect", "<f4", (3,)), ("samples", "<f4"), ("moments", "<f4", (2,)), ("flags", "<u4"), ("instance", "<i4"),
+                        ("rays", "<u4"), ("nodesVisited", "<u4"), ("trianglesTested", "<u4"), ("reserved", "<u4")]
+
+
+def _gi_sampling(gi_samples, gi_bounces, di_samples):
+    """RT64_GI_SAMPLING of the three overrides (-1: the last frame's value) -> (address or None for NULL, the struct to keep alive)."""
+    if gi_samples == -1 and gi_bounces == -1 and di_samples == -1:
+        return None, None
+    s = GI_SAMPLING(int(gi_samples), int(gi_bounces), int(di_samples), 0)
+    return C.addressof(s), s
+
+
+def _gi_points(points):
+    """The points argument of the indirect-light wrappers: an (N, 8) float32 array (position xyz, flags, normal xyz, instance; the two integers as bits), or a structured
+    array of GI_POINT_DTYPE, which is viewed as one."""
+    if not _is_torch(points):
+        import numpy as np
+        points = np.asarray(points)
+        if points.dtype.names is not None:
+            points = np.ascontiguousarray(points, dtype=np.dtype(GI_POINT_DTYPE)).view(np.float32).reshape(-1, 8)
+    return points
+
+
+def gi_rays(lib, view, points, slot, keys=None, gi_samples=-1, second_bounce=False, stream=None):
+    """RT64_GenerateViewPointGIRays: (N, 8) float32 RT64_GI_POINTs (or a structured array of GI_POINT_DTYPE) and, optionally, (N, 4) uint32 keys (None: point i is keyed
+    as pixel i of the last frame) -> (N, 8) float32 RT64_RAYs: the bounce ray of sample `slot` (giSamples .. 1) of every point as the frame's GI pass sends it, or with
+    `second_bounce` on the second bounce's noise slice (rule Y4).  `gi_samples` (1 .. 64) overrides the frame's value; -1 keeps it.  NumPy arrays take the host path; torch
+    CUDA tensors the device path, enqueued on `stream` like trace_rays."""
+    points = _gi_points(points)
+    k, keep_k = _sample_keys(points, keys, stream)
+    p, keep_p = _gi_sampling(gi_samples, -1, -1)
+    return _query(lib, view, "GenerateViewPointGIRays", "GenerateViewPointGIRaysDevice",
+                  [("in", points), ("value", k), ("value", p), ("value", int(slot)), ("value", GI_RAYS_SECOND_BOUNCE if second_bounce else 0), ("out", 8)], None, stream)
+
+
+def shade_gi_rays(lib, view, rays, hits, keys=None, incoming=None, di_samples=-1, stream=None):
+    """RT64_ComposeViewGIRays: (N, 8) float32 bounce rays, the (L, N, 8) float32 hits trace_view_ray_layers returned for them (RAY_FLAG_CULL_BACK_FACING, no lods), optional
+    (N, 4) uint32 keys and optional (N, 3) float32 `incoming` (None: the frame's ambient term) -> (N, 16) float32 RT64_GI_SAMPLEs: radiance rgb, remaining, position xyz,
+    flags, normal xyz, instance, layers, reserved, nodesVisited, trianglesTested (view the array through GI_SAMPLE_DTYPE): what one GI ray of the frame brings back (rules
+    Y5-Y7).  `di_samples` (0 .. 64) overrides the frame's value.  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream`."""
+    on_device = _is_torch(rays)
+    n = rays.shape[0] if hasattr(rays, "shape") and len(rays.shape) else -1
+    if on_device:
+        import torch
+        if not _is_torch(hits) or hits.dim() != 3 or hits.shape[2] != 8 or hits.dtype != torch.float32 or not hits.is_cuda:
+            raise ValueError("hits: an (L, N, 8) float32 CUDA tensor")
+        if incoming is not None and (not _is_torch(incoming) or tuple(incoming.shape) != (n, 3) or incoming.dtype != torch.float32 or not incoming.is_cuda):
+            raise ValueError("incoming: an (N, 3) float32 CUDA tensor")
+        hits = hits.contiguous(); incoming = incoming.contiguous() if incoming is not None else None
+        address = lambda a: a.data_ptr()
+    else:
+        import numpy as np
+        hits = np.ascontiguousarray(hits, dtype=np.float32)
+        if hits.ndim != 3 or hits.shape[2] != 8:
+            raise ValueError("hits: an (L, N, 8) float32 array")
+        if incoming is not None:
+            incoming = np.ascontiguousarray(incoming, dtype=np.float32)
+            if incoming.shape != (n, 3):
+                raise ValueError("incoming: an (N, 3) float32 array")
+        address = lambda a: a.ctypes.data
+    layers = _layer_count(hits.shape[0])
+    if hits.shape[1] != n:
+        raise ValueError("one list of hits per ray")
+    if on_device and stream is not None and stream != torch.cuda.current_stream(hits.device):
+        hits.record_stream(stream)
+        if incoming is not None:
+            incoming.record_stream(stream)
+    k, keep_k = _sample_keys(rays, keys, stream)
+    p, keep_p = _gi_sampling(-1, -1, di_samples)
+    return _query(lib, view, "ComposeViewGIRays", "ComposeViewGIRaysDevice",
+                  [("in", rays), ("value", address(hits)), ("value", layers), ("value", k), ("value", address(incoming) if incoming is not None else None), ("value", p), ("out", 16)], None, stream)
+
+
+def sample_indirect(lib, view, points, keys=None, gi_samples=-1, gi_bounces=-1, di_samples=-1, samples=False, stream=None):
+    """RT64_TraceViewPointsIndirect: (N, 8) float32 RT64_GI_POINTs (or a structured array of GI_POINT_DTYPE) and, optionally, (N, 4) uint32 keys -> (N, 12) float32
+    RT64_POINT_INDIRECTs: indirect rgb, samples, moments, flags, instance, rays, nodesVisited, trianglesTested, reserved (view the array through POINT_INDIRECT_DTYPE): the
+    indirect light of each point as the frame's GI pass computes it for the pixel of the key, without history (rule Y8).  `gi_samples` (0 .. 64), `gi_bounces` (1, 2) and
+    `di_samples` (0 .. 64) override the frame's values; -1 keeps them.  With `samples` -- it needs `gi_samples` given -- the result is (records, samples (S, N, 16)): the
+    first bounce's RT64_GI_SAMPLEs, sample slot S - k in block k.  NumPy arrays take the host path; torch CUDA tensors the device path, enqueued on `stream`."""
+    points = _gi_points(points)
+    if samples and gi_samples < 0:
+        raise ValueError("samples: give gi_samples, the array is sized by it")
+    k, keep_k = _sample_keys(points, keys, stream)
+    p, keep_p = _gi_sampling(gi_samples, gi_bounces, di_samples)
+    want = samples and gi_samples > 0
+    outs = _query(lib, view, "TraceViewPointsIndirect", "TraceViewPointsIndirectDevice",
+                  [("in", points), ("value", k), ("value", p), ("out", (int(gi_samples), 16) if want else None), ("out", 12)], None, stream)
+    if not samples:
+        return outs
+    if want:
+        return outs[1], outs[0]
+    return outs, outs[:0].reshape(0, outs.shape[0], 16) if not _is_torch(outs) else outs.new_empty((0, outs.shape[0], 16))
+
+
+def trace_indirect(lib, view, rays, lods=None, keys=None, gi_samples=-1, gi_bounces=-1, di_samples=-1, flags=0):
+    """RT64_TraceViewRayIndirect on an (N, 8) float32 NumPy array of rays (optional (N,) float32 lods and (N, 4) uint32 keys): the walk of trace_rays_alpha, the point of
+    each hit and the records of sample_indirect in one staging round trip per chunk -> (hits (N, 8), records (N, 12)); a miss gives a zero record with instance -1 (rule
+    Y10).  `flags`: RAY_FLAG_CULL_BACK_FACING only."""
+    k, keep_k = _sample_keys(rays, keys, None)
+    p, keep_p = _gi_sampling(gi_samples, gi_bounces, di_samples)
+    return _query(lib, view, "TraceViewRayIndirect", None, [("in", rays), ("out", 8), ("lods", lods), ("value", k), ("value", p), ("out", 12)], flags)
